@@ -10,8 +10,15 @@ per GPU) and gathered to rank 0 over RCCL, then assembled (strong scaling:
 the total work per step is fixed).  Rays = bounce segments counted as the
 reference counts them (main.cpp:390).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(and, with --dump-outputs DIR, writes what the last timed step computed as
+DIR/<name>.npy).  --full adds everything else the line can carry: the check of
+the last timed frame against the committed fixture, the distinct-samples and
+brute-force legs, the CPU baseline and, on several GPUs, the whole frame on one
+GPU alone (the one-GPU time and the bit-for-bit check of the gathered frame).
 """
 from __future__ import annotations
 
@@ -63,6 +70,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the frame check "
+                        "against the committed fixture, the extra legs (--legs), the CPU baseline and, on several "
+                        "GPUs, the one-GPU render the gathered frame is compared with")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps write what the last timed step computed (running mean, RGBA8 frame, "
+                        "ray count) as DIR/<name>.npy in float32/float64; a frame too large for 60 MB in all is "
+                        "written as a fixed seeded sample of its pixels (pixel_index.npy)")
     p.add_argument("--config", choices=sorted(CONFIGS) + ["onrender"], default="c2",
                    help="BASELINE.json workload preset; 'onrender': the reference's per-frame OnRender loop")
     p.add_argument("--width", type=int)
@@ -74,7 +89,7 @@ def parse():
     p.add_argument("--distance", type=float, help="camera distance from the look-at point (default: the scene's)")
     p.add_argument("--scalar", action="store_true", help="RenderTileScalar rules instead of RenderTile")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     p.add_argument("--band-rows", type=int, default=8, help="rows per interleaved band (multiple of 8)")
     p.add_argument("--verify", action="store_true",
                    help="after timing, rank 0 re-renders the whole frame alone and checks the gathered frame is "
@@ -86,7 +101,8 @@ def parse():
     p.add_argument("--devices", help="HIP devices of a single-process multi-GPU run (default 0..N-1)")
     p.add_argument("--transport", choices=("auto", "rccl", "peer"), default="auto",
                    help="single-process multi-GPU gather: RCCL, peer copies, or RCCL where it can be used")
-    p.add_argument("--no-verify", action="store_true", help="multi-GPU: skip the whole-frame check (on by default)")
+    p.add_argument("--no-verify", action="store_true",
+                   help="multi-GPU with --full: skip the whole-frame check (part of --full there)")
     p.add_argument("--frames", type=int, default=256, help="onrender: completed frames per measured run")
     p.add_argument("--modes", default="static,moving", help="onrender: camera modes to run (static, moving)")
     p.add_argument("--no-register", action="store_true",
@@ -107,7 +123,7 @@ def parse():
                    help="distinct leg: frames between its steps' first frames (default spp; 0 replays one range, "
                         "the leg's control)")
     p.add_argument("--legs", default="distinct,brute",
-                   help="extra legs after the timed steps (1 GPU, whole frame): 'distinct' (the same steps on "
+                   help="--full: extra legs after the timed steps (1 GPU, whole frame): 'distinct' (the same steps on "
                         "samples no launch has seen), 'brute' (the brute-force kernel's roofline), both, or 'none'")
     a = p.parse_args()
     if a.config == "onrender":
@@ -503,6 +519,39 @@ def roofline(args, info, kern_ms: float, rays_local: int, rows0: int, W: int, N:
     return roof
 
 
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes of --dump-outputs arrays in all
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(dst, rays: int, rgba8, accumulation=None):
+    """--dump-outputs: what the caller of the timed path holds after the last
+    timed step, as float32 / float64 .npy files under `dst`:
+      accumulation.npy  (pixels, 4) f32: the running mean (the v4 `prev` buffer; one device only)
+      rgba8.npy         (pixels, 4) f32: the stored sRGB frame, one byte per channel in memory order
+      rays.npy          (1,) f64: the segments the step counted
+    Frames too large for DUMP_BUDGET bytes in all are written as a sample of
+    their pixels, the same for every array and every run (a seeded choice
+    without replacement, sorted), listed in pixel_index.npy (f64)."""
+    import numpy as np
+    dst = pathlib.Path(dst)
+    dst.mkdir(parents=True, exist_ok=True)
+    n = rgba8.shape[0]
+    arrays = {"rgba8": rgba8.view(np.uint8).reshape(n, 4)}
+    if accumulation is not None:
+        arrays["accumulation"] = accumulation.reshape(n, 4)
+    per_pixel = 16 * len(arrays)
+    if n * per_pixel > DUMP_BUDGET:
+        k = DUMP_BUDGET // (per_pixel + 8)
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        arrays = {name: a[index] for name, a in arrays.items()}
+        np.save(dst / "pixel_index.npy", index.astype(np.float64))
+    elif (dst / "pixel_index.npy").exists():
+        (dst / "pixel_index.npy").unlink()  # an earlier, sampled dump into the same folder
+    for name, a in arrays.items():
+        np.save(dst / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    np.save(dst / "rays.npy", np.array([rays], dtype=np.float64))
+
+
 def base_line(args, *, world, elapsed, seg_counted, seg_folded, W, H, S, N, B, workload, parallelism, gather=None):
     value = seg_counted * args.steps / elapsed / 1e6
     seg_traced = seg_counted - seg_folded
@@ -755,12 +804,17 @@ def main_multi_device(args):
     minfo = multi.info()
     call_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
     frame = full.clone()
-    # the whole frame on devices[0] alone: the 1-GPU time on this box and the --verify reference
-    dev = rt.Device(d0, options=opts)
-    dev.upload_scene(scene)
-    ref, one_ms, one_rays = one_gpu_reference(rt, torch, dev, cam, args, W, H, S, B, stream, min(args.steps, 5))
-    verified = bool(torch.equal(frame, ref)) and one_rays == rays_per_step
-    frame_check = check_frame(rt, args, W, H, S, N, B, frame.cpu().numpy().view("uint32"), None, rays_per_step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rays_per_step, frame.cpu().numpy().view("uint32"))
+    dev, verified, frame_check = None, None, None
+    if args.full or args.verify:
+        # the whole frame on devices[0] alone: the 1-GPU time of this host and the --verify reference
+        dev = rt.Device(d0, options=opts)
+        dev.upload_scene(scene)
+        ref, one_ms, one_rays = one_gpu_reference(rt, torch, dev, cam, args, W, H, S, B, stream, min(args.steps, 5))
+        verified = bool(torch.equal(frame, ref)) and one_rays == rays_per_step
+    if args.full:
+        frame_check = check_frame(rt, args, W, H, S, N, B, frame.cpu().numpy().view("uint32"), None, rays_per_step)
     workload = workload_name(args, W, H, S, N, B, opts)
     gather = ("RCCL grouped send/recv to devices[0] (ncclCommInitAll) + rt_assemble scatter, overlapping the next "
               "call's traces" if minfo["Transport"] == rt.RT_MULTI_RCCL else
@@ -783,12 +837,15 @@ def main_multi_device(args):
     line["call_ms_events"] = round(call_ms, 3)
     # launch-buffer (re)allocations during the timed calls, over every device (rt_multi_reserve sized them: 0)
     line["buffer_growths_timed"] = growths
-    line["one_gpu"] = {"ms_per_frame": round(one_ms, 3), "device": d0,
-                       "speedup_vs_one_gpu": round(one_ms / (elapsed / args.steps * 1e3), 3),
-                       "note": "the same frame traced whole on devices[0] alone, in this run"}
-    line["verified_vs_one_gpu"] = verified
-    line["frame_check"] = frame_check
-    line["verified"] = combine_verified(verified, frame_check["verified"])
+    if verified is not None:
+        line["one_gpu"] = {"ms_per_frame": round(one_ms, 3), "device": d0,
+                           "speedup_vs_one_gpu": round(one_ms / (elapsed / args.steps * 1e3), 3),
+                           "note": "the same frame traced whole on devices[0] alone, in this run"}
+        line["verified_vs_one_gpu"] = verified
+    if frame_check is not None:
+        line["frame_check"] = frame_check
+    if verified is not None or frame_check is not None:
+        line["verified"] = combine_verified(verified, frame_check["verified"] if frame_check else None)
     # the roofline of the slowest device's share (its trace kernel; counters: the committed share record)
     slowest = max(range(len(devices)), key=lambda i: per_dev_ms[i])
     rows0 = rt.band_local_rows(H, band_rows, args.gpus, slowest)
@@ -799,9 +856,10 @@ def main_multi_device(args):
         line["config"]["device_options"] = opts
     line["roofline"]["device"] = slowest
     print(json.dumps(line), flush=True)
-    dev.close()
+    if dev is not None:
+        dev.close()
     multi.close()
-    if line["verified"] is False:
+    if line.get("verified") is False:
         print(f"bench.py: the gathered frame does NOT match: {frame_check}", file=sys.stderr)
         raise SystemExit(3)
 
@@ -856,7 +914,7 @@ def main_onrender(args):
                     warm += int(ok)
                 if has_profile:
                     rt.on_render_profile(reset=True)
-                done = rays = calls = 0
+                done = rays = calls = last_rays = 0
                 t0 = time.perf_counter()
                 while done < args.frames:
                     ok, r, _ = rt.on_render(img, scene, True, keys)
@@ -864,7 +922,10 @@ def main_onrender(args):
                     if ok:
                         done += 1
                         rays += r
+                        last_rays = r
                 wall = time.perf_counter() - t0
+                if args.dump_outputs and not runs:  # the headline run's last completed frame
+                    dump_outputs(args.dump_outputs, last_rays, img.reshape(-1))
                 run = {"devices": devs, "width": W, "height": H, "mode": mode,
                        "image": "staged" if args.no_register else "registered", "frames": done, "calls": calls,
                        "rays": rays, "mrays_per_s": round(rays / wall / 1e6, 1),
@@ -1069,8 +1130,14 @@ def main():
     timed_counts = ctr[first_timed:first_timed + args.steps].tolist()
     if any(n != rays_local for n in timed_counts):
         raise SystemExit(f"bench.py: timed steps counted {timed_counts} segments, expected {rays_local} each")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs as its caller holds them (a band share: that band's rows)
+        torch.cuda.synchronize()
+        last = full if world > 1 else cur[(state["n"] - 1) % 2]
+        dump_outputs(args.dump_outputs, int(rays_per_step[0].item()) if world > 1 else timed_counts[-1],
+                     last.cpu().numpy().view("uint32"), prev.cpu().numpy() if world == 1 else None)
     verified, one_ms = None, None
-    if (args.verify or world > 1) and not args.no_verify and bands == world:
+    if (args.verify or (world > 1 and args.full)) and not args.no_verify and bands == world:
         # rank 0 renders the whole frame alone: the 1-GPU time and the reference the gathered frame must equal
         if rank == 0:
             ref_cur, one_ms, one_rays = one_gpu_reference(rt, torch, dev, cam, args, W, H, S, B, stream,
@@ -1080,7 +1147,7 @@ def main():
         if world > 1:
             dist.barrier()
     frame_check = None
-    if rank == 0 and bands == world:
+    if args.full and rank == 0 and bands == world:
         # the last timed frame against the committed fixture of this workload
         last = full if world > 1 else cur[(state["n"] - 1) % 2]
         torch.cuda.synchronize()
@@ -1109,7 +1176,7 @@ def main():
         dev.close()
         return
     legs = {}
-    want = set() if args.headline_only else set(args.legs.split(","))
+    want = set(args.legs.split(",")) if args.full and not args.headline_only else set()
     if world == 1 and bands == 1:
         if "distinct" in want:
             legs["distinct"] = distinct_leg(rt, torch, args, dev, scene, cam, W, H, S, N, B, gpu, stream, opts)
@@ -1152,13 +1219,14 @@ def main():
             line["verified_vs_one_gpu"] = verified
         if frame_check is not None:
             line["frame_check"] = frame_check
-            line["verified"] = combine_verified(verified, frame_check["verified"])
-        if world == 1 and not args.no_cpu_baseline:
+        if verified is not None or frame_check is not None:
+            line["verified"] = combine_verified(verified, frame_check["verified"] if frame_check else None)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, total_rays)
         print(json.dumps(line), flush=True)
         if line.get("verified") is False:
-            print(f"bench.py: the timed frame does NOT match {frame_check.get('golden')}: {frame_check}",
-                  file=sys.stderr)
+            print(f"bench.py: the timed frame does NOT match {(frame_check or {}).get('golden')}: {frame_check}, "
+                  f"one-GPU render: {verified}", file=sys.stderr)
             raise SystemExit(3)
         bad = [k for k, leg in (("distinct samples", legs.get("distinct", {}).get("verified_vs_fresh_device")),
                                 ("brute force", legs.get("brute", {}).get("verified"))) if leg is False]

@@ -33,7 +33,7 @@ for r in $(seq $ROUNDS); do
     for c in "${CFG[@]}"; do
       args=$c; [ "$c" = "c2" ] && args=""
       split_variant "$v"
-      env "${VENV[@]}" RT_X=0 timeout -k 10 180 python bench.py --steps ${STEPS:-10} --warmup ${WARMUP:-6} --no-cpu-baseline \
+      env "${VENV[@]}" RT_X=0 timeout -k 10 180 python bench.py --steps ${STEPS:-10} --warmup ${WARMUP:-6} --full --no-cpu-baseline \
         --legs ${LEGS:-none} "${VARGS[@]}" $args \
         > gpurun_out/ab.json 2> gpurun_out/ab.err || { tail -20 gpurun_out/ab.err; exit 1; }
       python - "$r" "$v" "$c" <<'PY'

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 tag=$1; shift
 first=1
 for c in "$@"; do
-  extra="--no-cpu-baseline"; [ $first = 1 ] && extra=""; first=0
+  extra="--full --no-cpu-baseline"; [ $first = 1 ] && extra="--full"; first=0
   timeout -k 10 300 python bench.py --config $c $extra > gpurun_out/bench_${tag}_$c.json 2> gpurun_out/bench_${tag}_$c.err || { tail -20 gpurun_out/bench_${tag}_$c.err; exit 1; }
   python -c "import json; d=json.load(open('gpurun_out/bench_${tag}_$c.json')); print('$c', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['cold_ms'], d['segments'])"
 done

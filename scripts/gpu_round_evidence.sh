@@ -19,25 +19,25 @@ if [ "$part" = suite ]; then
   tail -1 ${W}_pytest.log
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > ${W}_smoke.log 2>&1 || { tail -5 ${W}_smoke.log; exit 1; }
   tail -1 ${W}_smoke.log
-  timeout -k 10 300 python bench.py > ${W}_bench.json 2> ${W}_bench.err || { tail -5 ${W}_bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full > ${W}_bench.json 2> ${W}_bench.err || { tail -5 ${W}_bench.err; exit 1; }
   tail -c 300 ${W}_bench.json; echo
   cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${W}_trace -o run --output-format csv -- python bench.py \
-    > ${W}_trace.log 2>&1 || { tail -5 ${W}_trace.log; exit 1; }
-  # the headline's timed launches alone (--legs none): the last 5 dispatches of its kernel are the 5 timed steps
+    --full > ${W}_trace.log 2>&1 || { tail -5 ${W}_trace.log; exit 1; }
+  # the headline's timed launches alone (a plain run): the last 5 dispatches of its kernel are the 5 timed steps
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${W}_trace_headline -o run --output-format csv -- python bench.py \
-    --legs none --no-cpu-baseline > ${W}_trace_headline.log 2>&1 || { tail -5 ${W}_trace_headline.log; exit 1; }
+    > ${W}_trace_headline.log 2>&1 || { tail -5 ${W}_trace_headline.log; exit 1; }
   f=$(find ${W}_trace_headline -name "*kernel_trace.csv" | head -1)
   python scripts/kernel_timeline.py "$f" --tail 5 --kernel "trace_kernel<true, 0, true" > ${W}_timeline.txt || exit 1
   for cfg in c3 rtw c2in; do
-    timeout -k 10 300 python bench.py --config $cfg --steps 5 --warmup 3 --no-cpu-baseline --legs distinct \
+    timeout -k 10 300 python bench.py --config $cfg --steps 5 --warmup 3 --full --no-cpu-baseline --legs distinct \
       >> ${W}_configs.jsonl 2>> ${W}_configs.err || exit 1
   done
-  timeout -k 10 300 python bench.py --brute --steps 5 --warmup 3 --no-cpu-baseline --legs none >> ${W}_configs.jsonl \
+  timeout -k 10 300 python bench.py --brute --steps 5 --warmup 3 --full --no-cpu-baseline --legs none >>${W}_configs.jsonl \
     2>> ${W}_configs.err || exit 1
-  timeout -k 10 300 python bench.py --config c5 --steps 2 --warmup 2 --no-cpu-baseline --legs none >> ${W}_configs.jsonl \
+  timeout -k 10 300 python bench.py --config c5 --steps 2 --warmup 2 --full --no-cpu-baseline --legs none >>${W}_configs.jsonl \
     2>> ${W}_configs.err || exit 1
-  BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --config c5 --gpus 8 --steps 1 --warmup 2 >> ${W}_configs.jsonl \
+  BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --config c5 --gpus 8 --steps 1 --warmup 2 --full >>${W}_configs.jsonl \
     2>> ${W}_configs.err || exit 1
   echo suite done
 elif [ "$part" = pmc ]; then

@@ -24,7 +24,7 @@ def run(ranks: int, port: int) -> dict:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", str(ranks),
            "--width", "320", "--height", "200", "--spp", "8", "--steps", "2", "--warmup", "2", "--verify",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     t = time.time()
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     out = {"ranks": ranks, "rc": p.returncode, "seconds": round(time.time() - t, 1)}
@@ -42,7 +42,8 @@ def run_single_process(ranks: int, extra) -> dict:
     refuses a repeated device)."""
     env = dict(os.environ, BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(ranks), "--verify", "--no-cpu-baseline", *extra]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(ranks), "--verify", "--full",
+           "--no-cpu-baseline", *extra]
     t = time.time()
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     out = {"ranks": ranks, "launcher": "none", "args": extra, "rc": p.returncode, "seconds": round(time.time() - t, 1)}

@@ -196,6 +196,44 @@ def test_bench_finds_the_fixture_of_each_preset():
     assert bench.combine_verified(None, None) is None
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files of the last timed
+    step's outputs; whole when they fit the byte budget, else the same seeded
+    pixel sample of every array on every run (pixel_index.npy)."""
+    import sys
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    rng = np.random.default_rng(11)
+    n = 1000
+    rgba = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    acc = rng.random((n, 4), dtype=np.float32)
+    bench.dump_outputs(tmp_path / "whole", 12345678901, rgba, acc)
+    got = {f.name: np.load(f) for f in (tmp_path / "whole").iterdir()}
+    assert sorted(got) == ["accumulation.npy", "rays.npy", "rgba8.npy"]
+    assert got["accumulation.npy"].dtype == np.float32 and np.array_equal(got["accumulation.npy"], acc)
+    assert got["rgba8.npy"].dtype == np.float32
+    assert np.array_equal(got["rgba8.npy"].astype(np.uint8).reshape(-1).view(np.uint32), rgba)
+    assert got["rays.npy"].dtype == np.float64 and got["rays.npy"].tolist() == [12345678901.0]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8000)
+    for name in ("a", "b"):
+        bench.dump_outputs(tmp_path / name, 7, rgba, acc)
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert sorted(a) == ["accumulation.npy", "pixel_index.npy", "rays.npy", "rgba8.npy"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 8000 + 8
+    index = a["pixel_index.npy"].astype(np.int64)
+    assert len(index) == 8000 // 40 and np.all(np.diff(index) > 0) and index[-1] < n
+    assert np.array_equal(a["accumulation.npy"], acc[index])
+    assert np.array_equal(a["rgba8.npy"], rgba.view(np.uint8).reshape(n, 4)[index].astype(np.float32))
+    # the frame alone (several GPUs: no running mean on the gathering device)
+    bench.dump_outputs(tmp_path / "c", 7, rgba)
+    assert sorted(f.name for f in (tmp_path / "c").iterdir()) == ["pixel_index.npy", "rays.npy", "rgba8.npy"]
+    assert len(np.load(tmp_path / "c" / "rgba8.npy")) == 8000 // 24
+
+
 def test_device_options_are_checked_before_any_device(rt):
     """rt_device_options (rt_device_create_ex) replaces the environment knobs the
     library read before round 6: bad values are refused before the call looks
