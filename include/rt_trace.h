@@ -501,6 +501,13 @@ int64_t rt_debug_masks(rt_device *dev, uint64_t *out, uint64_t max_words);
  * Arrays may be NULL to query the count. */
 int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, float *out_r2, float *out_r2p, uint32_t capacity,
                        uint32_t *out_count, uint32_t *out_flags);
+/* The packed sphere-group records rt_scene_upload builds for one rule set, as
+ * the device reads them (layout: rt_kernel.h, "HBM layout of an uploaded
+ * scene").  *out_f4 = float4 rows; out_rows (optional, 6 words) = rows per
+ * group, then the row index of x, y, z, r*r and the prefilter threshold.  out
+ * may be NULL to query the size.  Test/inspection hook. */
+int rt_scene_groups(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4, uint32_t *out_f4,
+                    uint32_t *out_rows);
 /* The clustered secondary-ray prefilter table rt_scene_upload builds for one
  * rule set (layout: rt_kernel.h, kClEntryF4 = 4 float4 rows per entry;
  * cluster-pair entries first).  *out_f4 = float4 rows, *out_cpairs = cluster

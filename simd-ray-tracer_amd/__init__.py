@@ -199,6 +199,7 @@ SIGNATURES = {
                                    POINTER(c_uint32)]),
     "rt_scene_clusters": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32),
                                   POINTER(c_uint32)]),
+    "rt_scene_groups": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32), c_void_p]),
     "rt_scene_cluster_layout": (c_int, [POINTER(RtScene), c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
     "rt_last_error": (c_char_p, []),
     "rt_on_init": (c_int, [POINTER(RtInitParams)]),
@@ -334,6 +335,21 @@ def scene_prefilter(scene: RtScene, simd: bool = True):
     _check(lib().rt_scene_prefilter(ctypes.byref(scene), int(simd), r2.ctypes.data, r2p.ctypes.data, n.value,
                                     ctypes.byref(n), ctypes.byref(fl)), "rt_scene_prefilter")
     return r2, r2p, int(fl.value)
+
+
+def scene_groups(scene: RtScene, simd: bool = True):
+    """The packed group records rt_scene_upload builds (rt_scene_groups): (records
+    (n_groups, rows, 4) f32, layout dict of the row indices rt_kernel.h names)."""
+    nf4 = c_uint32()
+    rows = np.zeros(6, np.uint32)
+    _check(lib().rt_scene_groups(ctypes.byref(scene), int(simd), None, 0, ctypes.byref(nf4), rows.ctypes.data),
+           "rt_scene_groups")
+    tab = np.zeros((nf4.value, 4), np.float32)
+    if nf4.value:
+        _check(lib().rt_scene_groups(ctypes.byref(scene), int(simd), tab.ctypes.data, nf4.value, ctypes.byref(nf4),
+                                     None), "rt_scene_groups")
+    layout = dict(zip(("kGroupF4", "kRowX", "kRowY", "kRowZ", "kRowR2", "kRowR2P"), (int(v) for v in rows)))
+    return tab.reshape(-1, layout["kGroupF4"], 4), layout
 
 
 def scene_clusters(scene: RtScene, simd: bool = True):

@@ -34,7 +34,7 @@ struct rt_device {
     uint32_t sec_threshold = 0;  // 0: per scene (rt_trace), else rt_device_options SecondaryThreshold
     int prefilter_env = -1;  // options Prefilter: -1 auto, 0 off, 1 on
     uint32_t prefilter[2] = {0, 0};  // per rule set, decided at upload
-    uint32_t pf_relative[2] = {0, 0};  // per rule set: row 3 holds r^2, per-lane thresholds (rt_kernel.hip kPfRel)
+    uint32_t pf_relative[2] = {0, 0};  // per rule set: the threshold row holds r^2, per-lane thresholds (rt_kernel.hip kPfRel)
     int pf_rel_env = -1;  // options PrefilterRelative: -1 auto (where the scene-wide bound does not pay), 0 never, 1 always
     uint32_t fast_sqrt[2] = {0, 0};  // per rule set: candidate sqrt in sqrt_rn's verified range
     float4 *d_clusters[2] = {nullptr, nullptr};  // clustered prefilter tables (cluster_table)
@@ -865,7 +865,7 @@ struct PackedSet {
     std::vector<float> groups, mats;
     uint32_t n_groups = 0;
     bool prefilter_pays = false;
-    bool relative = false;  // row 3 rewritten to r^2 / -inf for the per-lane threshold
+    bool relative = false;  // the threshold row (kRowR2P) rewritten to r^2 / -inf for the per-lane threshold
     uint32_t fast_sqrt = 0;
     std::vector<float> clusters;  // cluster_table
     uint32_t n_cpairs = 0, cl_words = 0;
@@ -924,7 +924,7 @@ static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env 
     // Where the scene-wide bound M_j makes r2p useless (a huge sphere: RTWeekend's
     // ground), the thresholds are formed per lane from the lane's own |C|^2 instead
     // (rt_kernel.hip kPfRel, kClRel): the cluster table is built for that rule, and
-    // row 3 then holds r^2 (-inf: never hit).
+    // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
     p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
     p.n_cpairs = cluster_table(gv, n, p.clusters, &p.cl_words, p.relative, &p.cl_levels, &p.cl_sub_pairs, cluster_k,
                                sub_spheres);
@@ -1002,6 +1002,25 @@ extern "C" int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, f
         const size_t base = (size_t)(s / 4u) * 4u * kGroupF4 + s % 4u;
         if (out_r2) out_r2[s] = p.groups[base + 4u * kRowR2];
         if (out_r2p) out_r2p[s] = p.groups[base + 4u * kRowR2P];
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_groups(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
+                               uint32_t *out_f4, uint32_t *out_rows) {
+    if (!scene || !out_f4) return fail(RT_EINVAL, "rt_scene_groups: NULL argument");
+    PackedSet p;
+    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
+    if (rc) return rc;
+    const uint32_t nf4 = p.n_groups * kGroupF4;
+    *out_f4 = nf4;
+    if (out_rows) {
+        const uint32_t rows[6] = {kGroupF4, kRowX, kRowY, kRowZ, kRowR2, kRowR2P};
+        memcpy(out_rows, rows, sizeof rows);
+    }
+    if (out) {
+        if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_groups: capacity %u < %u", capacity_f4, nf4);
+        memcpy(out, p.groups.data(), (size_t)nf4 * 16u);
     }
     return RT_OK;
 }
@@ -1273,6 +1292,9 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
         else if (a.cl_words == 2u) a.walk = a.pf_relative ? kWalkCl2Rel : kWalkCl2;
         else a.walk = a.pf_relative ? kWalkCl4Rel : kWalkCl4;
         if (d->walk_any_env) a.walk = kWalkAny;
+        // the walk kernels hold only the short candidate square root (rt_kernel.hip kFastSqrt): a scene
+        // with an r^2 outside its proven range takes the run-time kernel and its IEEE square root
+        if (!a.fast_sqrt) a.walk = kWalkAny;
     }
     const int src = a.scene_in_lds ? d->src : kSrcSmem;  // a scene in HBM is read through the scalar cache
     const uint32_t n_tiles = rtk_tile_count(desc->Width, local_rows, lpp);

@@ -8,8 +8,8 @@
 enum { kSrcSmem = 0, kSrcLds = 1 };  // where the sphere loop reads its groups
 constexpr uint32_t kGroupF4 = 5;      // float4 rows per sphere group:
 constexpr uint32_t kRowX = 0, kRowY = 1, kRowZ = 2;  //   centres
-constexpr uint32_t kRowR2P = 3;       //   prefilter thresholds (rows 0-3 = one s_load_dwordx16)
-constexpr uint32_t kRowR2 = 4;        //   r*r
+constexpr uint32_t kRowR2 = 3;        //   r*r (rows 0-3 = one s_load_dwordx16: all the exact test reads)
+constexpr uint32_t kRowR2P = 4;       //   prefilter thresholds (the per-group prefilter loop only)
 constexpr uint32_t kSphereF4 = 4;     // float4 rows per sphere record (TraceArgs.materials)
 enum { kFlagAccumZero = 1, kFlagSrgbPow = 2 };
 // Clustered secondary-ray prefilter (rt_host.cpp cluster_table): entries of
@@ -40,7 +40,8 @@ constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_
                                          // 121 groups: 11.3k Mrays/s clustered against 9.4k per group)
 
 // HBM layout of an uploaded scene (per rule set):
-//   groups    : n_groups x 5 float4 = {x[4]}, {y[4]}, {z[4]}, {r2p[4]}, {r*r[4]}  (80 B/group)
+//   groups    : n_groups x 5 float4 = {x[4]}, {y[4]}, {z[4]}, {r*r[4]}, {r2p[4]}  (80 B/group)
+//               rows 0-3 are what an exact test reads (the cluster walk's recheck: one scalar load);
 //               r2p = prefilter threshold of the secondary-ray sphere loop (rt_host.cpp);
 //               with pf_relative, r*r again (-inf: never hit) and the threshold is formed per lane
 //   spheres   : 4*n_groups records of kSphereF4 float4 = {centre.xyz, 0}, {Color.xyz, Specular},
@@ -79,7 +80,7 @@ struct TraceArgs {
     uint32_t lut_in_lds;         // rsqrt table in the LDS image (else read from HBM: rtk_lut_in_lds)
     uint32_t fold_in_lds;        // running-mean weight table in the LDS image (else computed: rtk_fold_in_lds)
     uint32_t scene_in_lds;       // groups + materials copied into the LDS image (else read from HBM: GS kernels)
-    uint32_t pf_relative;        // prefilter: row 3 holds r^2 and the threshold is per lane (rt_kernel.hip kPfRel)
+    uint32_t pf_relative;        // prefilter: row kRowR2P holds r^2 and the threshold is per lane (rt_kernel.hip kPfRel)
     uint32_t solo;               // one wave per workgroup (4 x tiles workgroups of 64 threads; needs no LDS image)
     uint32_t walk;               // kWalk*: the one-wave kernel specialised for this launch's secondary walk
     // optional: live block tiles of the cull pass, on the device (kCullTotals).  Set while the host

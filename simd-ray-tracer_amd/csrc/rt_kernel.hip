@@ -368,12 +368,30 @@ __device__ __forceinline__ void group_rows(Group &G, float4 x, float4 y, float4 
 // Group rows from the constant address space: read-only for the kernel's
 // lifetime, so a wave-uniform address always becomes s_loads into SGPRs
 // (immediate offsets from one base: rows 0-3 one dwordx16, row 4 a dwordx4).
+// Rows 0-3 hold the centres and r*r, all an exact test reads; row 4 the prefilter thresholds.
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) v4f_t cv4f_t;
 __device__ __forceinline__ float4 f4(v4f_t v) { return make_float4(v.x, v.y, v.z, v.w); }
+// Rows 0-3 of a group record or of a cluster-table entry: one contiguous 64 B
+// block at a 16 B aligned address, read as ONE s_load_dwordx16 (row by row the
+// backend issued a dwordx8 and two dwordx4 for it: three scalar-memory
+// instructions and their address setup per entry of the walk).
+typedef float v16f_t __attribute__((ext_vector_type(16)));
+typedef v16f_t v16f_a16_t __attribute__((aligned(16)));
+typedef const __attribute__((address_space(4))) v16f_a16_t cv16f_t;
+struct Rows4 {
+    v4f_t r0, r1, r2, r3;
+};
+__device__ __forceinline__ Rows4 load_rows4(cv4f_t *e) {
+    const v16f_t v = *(cv16f_t *)e;
+    return {__builtin_shufflevector(v, v, 0, 1, 2, 3), __builtin_shufflevector(v, v, 4, 5, 6, 7),
+            __builtin_shufflevector(v, v, 8, 9, 10, 11), __builtin_shufflevector(v, v, 12, 13, 14, 15)};
+}
+static_assert(kRowX == 0 && kRowY == 1 && kRowZ == 2 && kRowR2 == 3 && kRowR2P == 4, "group rows 0-3: centres and r*r");
 __device__ __forceinline__ Group load_group_at(cv4f_t *cg) {
     Group G;
-    group_rows(G, f4(cg[kRowX]), f4(cg[kRowY]), f4(cg[kRowZ]), f4(cg[kRowR2P]), f4(cg[kRowR2]));
+    const Rows4 r = load_rows4(cg);
+    group_rows(G, f4(r.r0), f4(r.r1), f4(r.r2), f4(cg[kRowR2P]), f4(r.r3));
     return G;
 }
 
@@ -511,25 +529,23 @@ __device__ __forceinline__ f2 pair_prefilter(const RayPk &r, f2 sx, f2 sy, f2 sz
 // reruns the exact packed test (same ops as test_group) and the exact candidate
 // logic decides, so results are identical.  (Measured: +5.5 % on C2 over one
 // exact recheck of both pairs per flagged group.)
-// The prefilter needs rows 0-3 only (SGPRs); r^2 of a flagged group comes
-// from the block's LDS copy.
 // The exact recheck of one group's flagged sphere pairs (f01, f23): only such
 // a pair reruns the exact packed test (same ops as test_group) and the exact
 // candidate logic decides, so results are identical.
-// GS (scenes beyond the LDS image, rt_kernel.h kMaxLdsGroups): the group's r^2
-// row (wave-uniform g) comes through the scalar cache instead of LDS.
-template <bool SIMD, bool GS>
-__device__ __forceinline__ void recheck_pairs(const TraceArgs &a, const float4 *lds_groups, const Group &G, uint32_t g,
-                                              const RayPk &p, Hit &h, bool f01, bool f23) {
-    const float4 r2 = GS ? f4(((cv4f_t *)a.groups)[kGroupF4 * g + kRowR2]) : lds_groups[kGroupF4 * g + kRowR2];
+// The group's r^2 row comes with its centres (rows 0-3 of the record, one
+// scalar load: load_group_exact_at / load_group_at).
+template <bool SIMD>
+__device__ __forceinline__ void recheck_pairs(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
+                                              bool f01, bool f23) {
+    const float4 r2 = make_float4(G.r2[0], G.r2[1], G.r2[2], G.r2[3]);
     if (f01) {
         f2 T01;
         const f2 d01 = pair_dist(p, f2{G.x[0], G.x[1]}, f2{G.y[0], G.y[1]}, f2{G.z[0], G.z[1]}, T01);
         const uint32_t s0 = 4u * g;
         const bool h0 = SIMD ? d01.x < r2.x : s0 + 0u < a.n_spheres && !(d01.x > r2.x);
         const bool h1 = SIMD ? d01.y < r2.y : s0 + 1u < a.n_spheres && !(d01.y > r2.y);
-        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, r2.x, a.fast_sqrt != 0u);
-        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, r2.y, a.fast_sqrt != 0u);
+        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, r2.x, fast);
+        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, r2.y, fast);
     }
     if (f23) {
         f2 T23;
@@ -537,13 +553,13 @@ __device__ __forceinline__ void recheck_pairs(const TraceArgs &a, const float4 *
         const uint32_t s0 = 4u * g;
         const bool h2 = SIMD ? d23.x < r2.z : s0 + 2u < a.n_spheres && !(d23.x > r2.z);
         const bool h3 = SIMD ? d23.y < r2.w : s0 + 3u < a.n_spheres && !(d23.y > r2.w);
-        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, r2.z, a.fast_sqrt != 0u);
-        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, r2.w, a.fast_sqrt != 0u);
+        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, r2.z, fast);
+        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, r2.w, fast);
     }
 }
 
 // Per-lane ("relative") prefilter threshold: t = RN(cc * 2^-15 + r^2) with
-// cc = the lane's computed |C|^2, where row 3 holds r^2 (-inf: never hit).
+// cc = the lane's computed |C|^2, where the threshold row (kRowR2P) holds r^2 (-inf: never hit).
 // The error bound of e (and of the reference-rounded dist) scales with the
 // lane's own |C|^2 instead of the scene-wide M_j, so the test still proves
 // misses in scenes whose M_j bound is useless (RTWeekend's ground sphere
@@ -578,7 +594,7 @@ struct PfStats {
 
 template <bool SIMD, bool GS, bool REL>
 __device__ __forceinline__ void test_group_pf(const TraceArgs &a, const float4 *lds_groups, const Group &G, uint32_t g,
-                                              const RayPk &p, Hit &h, PfStats *ps = nullptr) {
+                                              const RayPk &p, Hit &h, bool fast, PfStats *ps = nullptr) {
     bool f01, f23;
     prefilter_group<REL>(G, p, f01, f23);
     if (ps) {
@@ -586,25 +602,26 @@ __device__ __forceinline__ void test_group_pf(const TraceArgs &a, const float4 *
         ps->pairs += (__ballot(f01) != 0) + (__ballot(f23) != 0);
         ps->lane_pairs += __builtin_popcountll(__ballot(f01)) + __builtin_popcountll(__ballot(f23));
     }
-    if (f01 | f23) recheck_pairs<SIMD, GS>(a, lds_groups, G, g, p, h, f01, f23);
+    if (f01 | f23) recheck_pairs<SIMD>(a, G, g, p, h, fast, f01, f23);
 }
 
 template <bool SIMD>
-__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h,
+__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
                                            uint32_t *hit_groups);
 
-// Rows 0-3 only (one s_load_dwordx16): what the prefilter reads.
-__device__ __forceinline__ Group load_group_pf_at(cv4f_t *cg) {
+// Rows 0-3 only (one s_load_dwordx16): what the exact recheck of the cluster walk reads.
+__device__ __forceinline__ Group load_group_exact_at(cv4f_t *cg) {
     Group G;
     const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    group_rows(G, f4(cg[kRowX]), f4(cg[kRowY]), f4(cg[kRowZ]), f4(cg[kRowR2P]), z4);
+    const Rows4 r = load_rows4(cg);
+    group_rows(G, f4(r.r0), f4(r.r1), f4(r.r2), z4, f4(r.r3));
     return G;
 }
 
 // The full sphere loop over all groups from SGPRs.  PF: secondary rays
 // through the prefilter; else the exact test.
 template <bool SIMD, bool PF, bool GS, bool REL = false>
-__device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray, Hit &h,
+__device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray, Hit &h, bool fast,
                                                 uint32_t *hit_groups, PfStats *ps = nullptr) {
     cv4f_t *gp = (cv4f_t *)a.groups;
     // one group in SGPRs at a time: its s_load (scalar-cache hit) is covered
@@ -612,9 +629,9 @@ __device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4
     // prefetch, at half the SGPRs (and two groups per trip under one branch
     // measured 2 % slower)
     for (uint32_t g = 0; g < a.n_groups; ++g, gp += kGroupF4) {
-        const Group G = PF ? load_group_pf_at(gp) : load_group_at(gp);
-        if (PF) test_group_pf<SIMD, GS, REL>(a, lds_groups, G, g, ray, h, ps);
-        else test_group<SIMD>(a, G, g, ray, h, hit_groups);
+        const Group G = load_group_at(gp);
+        if (PF) test_group_pf<SIMD, GS, REL>(a, lds_groups, G, g, ray, h, fast, ps);
+        else test_group<SIMD>(a, G, g, ray, h, fast, hit_groups);
     }
 }
 
@@ -688,6 +705,40 @@ __device__ __forceinline__ void merge_words(uint64_t (&wave)[kClWords], uint64_t
     }
 }
 
+#ifndef RTK_MERGE1  // A/B: make variant KFLAGS=-DRTK_MERGE1=0 (the one-word merge left to the compiler)
+#define RTK_MERGE1 1
+#endif
+// One-word tables: wave |= (n0 & k0) ? bits0 : 0, then the same for member 1.  The
+// lane-mask conjunction's own SCC (result != 0) feeds the 64-bit select, so a member
+// costs and + select + or on the scalar unit (the compiler's lowering: and, compare,
+// two 32-bit selects, or).
+__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t n0, uint64_t k0, uint64_t bits0, uint64_t n1,
+                                            uint64_t k1, uint64_t bits1) {
+    uint64_t t;
+    asm("s_and_b64 %[t], %[n0], %[k0]\n\t"
+        "s_cselect_b64 %[t], %[b0], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]\n\t"
+        "s_and_b64 %[t], %[n1], %[k1]\n\t"
+        "s_cselect_b64 %[t], %[b1], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]"
+        : [w] "+&s"(wave), [t] "=&s"(t)
+        : [n0] "s"(n0), [k0] "s"(k0), [b0] "s"(bits0), [n1] "s"(n1), [k1] "s"(k1), [b1] "s"(bits1)
+        : "scc");
+}
+// (single lane masks: per-lane tables test no behind rule at the member level)
+__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t f0, uint64_t bits0, uint64_t f1, uint64_t bits1) {
+    uint64_t t;
+    asm("s_cmp_lg_u64 %[f0], 0\n\t"
+        "s_cselect_b64 %[t], %[b0], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]\n\t"
+        "s_cmp_lg_u64 %[f1], 0\n\t"
+        "s_cselect_b64 %[t], %[b1], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]"
+        : [w] "+&s"(wave), [t] "=&s"(t)
+        : [f0] "s"(f0), [b0] "s"(bits0), [f1] "s"(f1), [b1] "s"(bits1)
+        : "scc");
+}
+
 // an SGPR pointer the compiler cannot see through: loads through it stay where they are written
 __device__ __forceinline__ cv4f_t *opaque(cv4f_t *p) {
     asm volatile("" : "+s"(p));
@@ -747,12 +798,14 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
                                              uint64_t (&wave)[kClWords], const ClConst &k, PfStats *ps) {
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
     if (ps) ps->groups += count;
-    const uint32_t end = (first + count) * kEntryBytes;
+    // (the end offset opaque to the optimiser: it otherwise derives a trip count and runs a
+    // second, down-counting induction variable beside the offset -- one more SALU per entry)
+    uint32_t end = (first + count) * kEntryBytes;
+    if (RTK_MERGE1) asm volatile("" : "+s"(end));
     for (uint32_t off = first * kEntryBytes; off != end; off += kEntryBytes) {
         cv4f_t *e = cl_entry(ct, off);
-        const v4f_t r0 = e[0], r1 = e[1];
-        const v4f_t r3 = e[3];
-        const v4f_t r2 = W <= 2 ? e[2] : v4f_t{0.0f, 0.0f, 0.0f, 0.0f};
+        const Rows4 rows = load_rows4(e);  // (one scalar load per entry)
+        const v4f_t r0 = rows.r0, r1 = rows.r1, r2 = rows.r2, r3 = rows.r3;
         f2 T, cc;
         const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
         // a lane may hit the sphere: near the line, and not wholly behind the origin
@@ -765,13 +818,24 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
         // (RTWeekend +2.7 % same box; C2's scene-wide table loses 1.7 % without it).
         // Either way a skipped pair is a proven miss.
         constexpr bool kBehind = !REL;
-        const uint64_t f0m = kBehind ? ballot_and(!(v.x >= t0), !(T.x < b0)) : __builtin_amdgcn_ballot_w64(!(v.x >= t0));
-        const uint64_t f1m = kBehind ? ballot_and(!(v.y >= t1), !(T.y < b1)) : __builtin_amdgcn_ballot_w64(!(v.y >= t1));
+        const uint64_t n0m = __builtin_amdgcn_ballot_w64(!(v.x >= t0)), n1m = __builtin_amdgcn_ballot_w64(!(v.y >= t1));
+        if constexpr (W == 1 && RTK_MERGE1) {
+            const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
+            const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
+            if constexpr (kBehind)
+                merge_word1(wave[0], n0m, __builtin_amdgcn_ballot_w64(!(T.x < b0)), w0, n1m,
+                            __builtin_amdgcn_ballot_w64(!(T.y < b1)), w1);
+            else
+                merge_word1(wave[0], n0m, w0, n1m, w1);
+            continue;
+        }
+        const uint64_t f0m = kBehind ? n0m & __builtin_amdgcn_ballot_w64(!(T.x < b0)) : n0m;
+        const uint64_t f1m = kBehind ? n1m & __builtin_amdgcn_ballot_w64(!(T.y < b1)) : n1m;
         const bool f0 = f0m != 0, f1 = f1m != 0;
-        if constexpr (W == 1) {
-            const uint64_t b0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
-            const uint64_t b1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
-            wave[0] |= (f0 ? b0 : 0ull) | (f1 ? b1 : 0ull);
+        if constexpr (W == 1) {  // (the compiler's own lowering, A/B builds only: RTK_MERGE1=0)
+            const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
+            const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
+            wave[0] |= (f0 ? w0 : 0ull) | (f1 ? w1 : 0ull);
         } else if constexpr (W == 2) {
             uint64_t bw0[W], bw1[W];  // member 0 and 1 bits in word w
 #pragma unroll
@@ -783,14 +847,15 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
             merge_words<W>(wave, f0m, bw0);
             merge_words<W>(wave, f1m, bw1);
         } else {
-            // four-word tables: a member's four bit rows are read only when some lane flagged it (a
-            // uniform branch), so they do not hold 16 SGPRs across every entry's prefilter (RTWeekend
-            // +0.7 %; the two-word form keeps its selects: C5 -0.5 % this way, profiles/r05u_lazy_bits_ab.txt)
+            // four-word tables: a member's bit rows of words 1-3 are read only when some lane flagged it (a
+            // uniform branch), so they do not hold 12 SGPRs across every entry's prefilter (RTWeekend
+            // +0.7 %; the two-word form keeps its selects: C5 -0.5 % this way, profiles/r05u_lazy_bits_ab.txt);
+            // word 0's row came with the entry's one load
             if (f0 | f1) {
                 cv4f_t *eb = opaque(e);
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
-                    const v4f_t rb = w == 0 ? eb[2] : eb[3 + w];
+                    const v4f_t rb = w == 0 ? r2 : eb[3 + w];
                     if (f0) wave[w] |= (uint64_t)__float_as_uint(rb.x) | ((uint64_t)__float_as_uint(rb.y) << 32);
                     if (f1) wave[w] |= (uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32);
                 }
@@ -809,8 +874,10 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
 // of small spheres only near their origin).
 template <bool REL, bool SLAB = true, bool BEHIND = true>
 __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const ClConst &k, uint64_t &m0,
-                                             uint64_t &m1) {
-    const v4f_t r0 = e[0], r1 = e[1], r3 = e[3];
+                                             uint64_t &m1, v4f_t &ranges) {
+    const Rows4 rows = load_rows4(e);  // (one scalar load per entry; row 2 = the entry's ranges)
+    const v4f_t r0 = rows.r0, r1 = rows.r1, r3 = rows.r3;
+    ranges = rows.r2;
     f2 T, cc;
     const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
     if constexpr (REL) {
@@ -847,7 +914,7 @@ __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const 
 // its sub-clusters' members too.
 template <bool SIMD, int W, bool GS, bool REL>
 __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray,
-                                                 Hit &h, PfStats *ps) {
+                                                 Hit &h, bool fast, PfStats *ps) {
     cv4f_t *ct = (cv4f_t *)a.clusters;
     uint64_t wave[kClWords] = {0ull, 0ull, 0ull, 0ull};
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
@@ -862,8 +929,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         k.aux = f2{slab_e0, __builtin_fabsf(dy)};
     }
     // the member pairs of an entered (sub-)cluster pair entry
-    auto members = [&](cv4f_t *e, bool in0, bool in1) {
-        const v4f_t r2 = e[2];
+    auto members = [&](v4f_t r2, bool in0, bool in1) {
         if (ps) ps->lane_pairs += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
         if (in0) member_pairs<W, REL>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, wave, k, ps);
         if (in1) member_pairs<W, REL>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, wave, k, ps);
@@ -874,29 +940,30 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         for (uint32_t off = first * kEntryBytes, end = (first + count) * kEntryBytes; off != end; off += kEntryBytes) {
             cv4f_t *e = cl_entry(ct, off);
             uint64_t m0, m1;
+            v4f_t r2;
 #ifndef RTK_EXP_SUB
 #define RTK_EXP_SUB true, true
 #endif
-            cluster_pair<REL, RTK_EXP_SUB>(e, ray, k, m0, m1);
-            members(e, m0 != 0, m1 != 0);
+            cluster_pair<REL, RTK_EXP_SUB>(e, ray, k, m0, m1, r2);
+            members(r2, m0 != 0, m1 != 0);
         }
     };
     if (ps) ps->cl_tested += a.n_cpairs;
     for (uint32_t off = 0, end = a.n_cpairs * kEntryBytes; off != end; off += kEntryBytes) {
         cv4f_t *e = cl_entry(ct, off);
         uint64_t m0, m1;
+        v4f_t r2;
 #ifndef RTK_EXP_TOP
 #define RTK_EXP_TOP true, true
 #endif
-        cluster_pair<REL, RTK_EXP_TOP>(e, ray, k, m0, m1);
+        cluster_pair<REL, RTK_EXP_TOP>(e, ray, k, m0, m1, r2);
         if constexpr (kTwoLevels) {
-            const v4f_t r2 = e[2];
             if (ps) ps->lane_pairs += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
             if (ps) ps->cl_top_entered += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
             if (m0 != 0) subs(__float_as_uint(r2.x), __float_as_uint(r2.y));
             if (m1 != 0) subs(__float_as_uint(r2.z), __float_as_uint(r2.w));
         } else {
-            members(e, m0 != 0, m1 != 0);
+            members(r2, m0 != 0, m1 != 0);
         }
     }
     cv4f_t *gp = (cv4f_t *)a.groups;
@@ -909,7 +976,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
             const bool f01 = (m >> q) & 1u, f23 = (m >> (q + 1u)) & 1u;
             m &= ~(3ull << q);
             if (ps) ps->pairs += (f01 ? 1u : 0u) + (f23 ? 1u : 0u);
-            recheck_pairs<SIMD, GS>(a, lds_groups, load_group_pf_at(gp + kGroupF4 * g), g, ray, h, f01, f23);
+            recheck_pairs<SIMD>(a, load_group_exact_at(gp + kGroupF4 * g), g, ray, h, fast, f01, f23);
         }
     }
 }
@@ -917,7 +984,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
 // All four spheres of group g; one wave-level branch per group, nested
 // branches only for the (rare) lanes that pass the distance test.
 template <bool SIMD>
-__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h,
+__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
                                            uint32_t *hit_groups) {
     f2 T01, T23;
     const f2 d01 = pair_dist(p, f2{G.x[0], G.x[1]}, f2{G.y[0], G.y[1]}, f2{G.z[0], G.z[1]}, T01);
@@ -937,10 +1004,10 @@ __device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, u
     }
     if (hit_groups && __ballot(h0 | h1 | h2 | h3)) *hit_groups += 1;
     if (h0 | h1 | h2 | h3) {
-        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, G.r2[0], a.fast_sqrt != 0u);
-        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, G.r2[1], a.fast_sqrt != 0u);
-        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, G.r2[2], a.fast_sqrt != 0u);
-        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, G.r2[3], a.fast_sqrt != 0u);
+        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, G.r2[0], fast);
+        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, G.r2[1], fast);
+        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, G.r2[2], fast);
+        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, G.r2[3], fast);
     }
 }
 
@@ -974,7 +1041,7 @@ __device__ __forceinline__ f2 pair_dist_c(const RayPk &r, f2 cx, f2 cy, f2 cz, f
 // One sphere pair of a primary round (spheres L0, L0 + 1 of group g, camera-relative rows from
 // TraceArgs.prim): test_group's two halves as separate pair tests.
 template <bool SIMD, int L0>
-__device__ __forceinline__ void test_half_prim(const TraceArgs &a, uint32_t g, const RayPk &p, Hit &h, f2 cx, f2 cy,
+__device__ __forceinline__ void test_half_prim(const TraceArgs &a, uint32_t g, const RayPk &p, Hit &h, bool fast, f2 cx, f2 cy,
                                                f2 cz, float r2a, float r2b) {
     f2 T;
     const f2 d = pair_dist_c(p, cx, cy, cz, T);
@@ -988,8 +1055,8 @@ __device__ __forceinline__ void test_half_prim(const TraceArgs &a, uint32_t g, c
         hb = s0 + 1u < a.n_spheres && !(d.y > r2b);
     }
     if (ha | hb) {
-        if (ha) candidate<SIMD, L0>(h, g, T.x, d.x, r2a, a.fast_sqrt != 0u);
-        if (hb) candidate<SIMD, L0 + 1>(h, g, T.y, d.y, r2b, a.fast_sqrt != 0u);
+        if (ha) candidate<SIMD, L0>(h, g, T.x, d.x, r2a, fast);
+        if (hb) candidate<SIMD, L0 + 1>(h, g, T.y, d.y, r2b, fast);
     }
 }
 
@@ -997,12 +1064,12 @@ __device__ __forceinline__ void test_half_prim(const TraceArgs &a, uint32_t g, c
 // ascending order, the reference's sphere order, so the per-class minima and tie rules are those of
 // the full group loop.
 template <bool SIMD>
-__device__ __forceinline__ void test_pair_prim(const TraceArgs &a, cv4f_t *prim, uint32_t pr, const RayPk &p, Hit &h) {
+__device__ __forceinline__ void test_pair_prim(const TraceArgs &a, cv4f_t *prim, uint32_t pr, const RayPk &p, Hit &h, bool fast) {
     const uint32_t g = pr >> 1;
     cv4f_t *pg = prim + kPrimF4 * g;
     const v4f_t cx = pg[0], cy = pg[1], cz = pg[2], r2 = pg[3];
-    if (pr & 1u) test_half_prim<SIMD, 2>(a, g, p, h, f2{cx.z, cx.w}, f2{cy.z, cy.w}, f2{cz.z, cz.w}, r2.z, r2.w);
-    else test_half_prim<SIMD, 0>(a, g, p, h, f2{cx.x, cx.y}, f2{cy.x, cy.y}, f2{cz.x, cz.y}, r2.x, r2.y);
+    if (pr & 1u) test_half_prim<SIMD, 2>(a, g, p, h, fast, f2{cx.z, cx.w}, f2{cy.z, cy.w}, f2{cz.z, cz.w}, r2.z, r2.w);
+    else test_half_prim<SIMD, 0>(a, g, p, h, fast, f2{cx.x, cx.y}, f2{cy.x, cy.y}, f2{cz.x, cz.y}, r2.x, r2.y);
 }
 
 // Conservative per-wave culling for primary rays.  All primary rays of a
@@ -1157,6 +1224,9 @@ struct Shape {
 #endif
 constexpr int solo_waves(int walk) { return walk == kWalkCl2 ? RTK_SOLO_WAVES_CL2 : RTK_SOLO_WAVES_PER_SIMD; }
 
+#ifndef RTK_FAST_SQRT_KERNELS  // A/B: make variant KFLAGS=-DRTK_FAST_SQRT_KERNELS=0 (the flag tested at every site)
+#define RTK_FAST_SQRT_KERNELS 1
+#endif
 template <int WALK> struct Walk {
     // the per-group walk (small scenes) may merge primary and secondary rounds
     static constexpr bool MERGEABLE = WALK == kWalkAny || WALK == kWalkGroups;
@@ -1192,6 +1262,11 @@ void trace_kernel(TraceArgs a) {
     constexpr uint32_t NPIX = 64u / LP;  // pixels traced at a time
     constexpr bool kMergeable = Walk<WALK>::MERGEABLE;
     constexpr uint32_t kRing = Ring<LP>::N;
+    // The candidate square root (candidate<>): a walk-specialised one-wave kernel is launched only for
+    // scenes whose r^2 range the host proved (TraceArgs.fast_sqrt; launch_p), so it holds sqrt_rn alone --
+    // no flag test and no IEEE body at its candidate sites.  Every other kernel tests the flag.
+    constexpr bool kFastSqrt = RTK_FAST_SQRT_KERNELS && SOLO && WALK != kWalkAny;
+    const bool fast = kFastSqrt || a.fast_sqrt != 0u;
     extern __shared__ float4 smem[];
     // first launch of a key: the host has not read the live-tile count back, so
     // the grid covers every tile (live first) and blocks past the count leave
@@ -1614,7 +1689,7 @@ void trace_kernel(TraceArgs a) {
                             while (m) {  // the tile's sphere pairs, in the reference's order
                                 const uint32_t pr = w * 64u + (uint32_t)__builtin_ctzll(m);
                                 m &= m - 1;
-                                test_pair_prim<SIMD>(a, prim, pr, ray, h);
+                                test_pair_prim<SIMD>(a, prim, pr, ray, h, fast);
                             }
                         }
                     } else {
@@ -1633,28 +1708,28 @@ void trace_kernel(TraceArgs a) {
                             if (kStats && a.stats) st_pf_rounds += 1;
                             PfStats *ps = kStats && a.stats ? &st_pf : nullptr;
                             if constexpr (Walk<WALK>::CLUSTERS) {
-                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL>(a, lds_groups, ray, h, ps);
+                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL>(a, lds_groups, ray, h, fast, ps);
                             } else if constexpr (WALK == kWalkGroups) {
                                 __builtin_unreachable();  // the host runs kWalkGroups kernels without a cluster table
                             } else if (a.pf_relative) {
-                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, true>(a, lds_groups, ray, h, ps);
-                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, true>(a, lds_groups, ray, h, ps);
-                                else clustered_groups<SIMD, 4, GS, true>(a, lds_groups, ray, h, ps);
+                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, true>(a, lds_groups, ray, h, fast, ps);
+                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, true>(a, lds_groups, ray, h, fast, ps);
+                                else clustered_groups<SIMD, 4, GS, true>(a, lds_groups, ray, h, fast, ps);
                             } else {
-                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, false>(a, lds_groups, ray, h, ps);
-                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, false>(a, lds_groups, ray, h, ps);
-                                else clustered_groups<SIMD, 4, GS, false>(a, lds_groups, ray, h, ps);
+                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, false>(a, lds_groups, ray, h, fast, ps);
+                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, false>(a, lds_groups, ray, h, fast, ps);
+                                else clustered_groups<SIMD, 4, GS, false>(a, lds_groups, ray, h, fast, ps);
                             }
                         } else if (SRC == kSrcSmem && pf && a.pf_relative && !Walk<WALK>::CLUSTERS) {
                             if (kStats && a.stats) st_pf_rounds += 1;
-                            all_groups_smem<SIMD, true, GS, true>(a, lds_groups, ray, h, nullptr,
+                            all_groups_smem<SIMD, true, GS, true>(a, lds_groups, ray, h, fast, nullptr,
                                                                   kStats && a.stats ? &st_pf : nullptr);
                         } else if (SRC == kSrcSmem && pf && !Walk<WALK>::CLUSTERS) {
                             if (kStats && a.stats) st_pf_rounds += 1;
-                            all_groups_smem<SIMD, true, GS>(a, lds_groups, ray, h, nullptr,
+                            all_groups_smem<SIMD, true, GS>(a, lds_groups, ray, h, fast, nullptr,
                                                         kStats && a.stats ? &st_pf : nullptr);
                         } else if (SRC == kSrcSmem) {
-                            all_groups_smem<SIMD, false, GS>(a, lds_groups, ray, h,
+                            all_groups_smem<SIMD, false, GS>(a, lds_groups, ray, h, fast,
                                                              kStats && a.stats ? &st_sec_hit : nullptr);
                         } else {
                             // software-pipelined: group g+1's load is in flight while
@@ -1663,7 +1738,7 @@ void trace_kernel(TraceArgs a) {
                             for (uint32_t g = 0; g < a.n_groups; ++g) {
                                 const Group G = next;
                                 next = load_group<SRC>(a, lds_groups, g + 1u);
-                                test_group<SIMD>(a, G, g, ray, h, kStats && a.stats ? &st_sec_hit : nullptr);
+                                test_group<SIMD>(a, G, g, ray, h, fast, kStats && a.stats ? &st_sec_hit : nullptr);
                             }
                         }
                     }
@@ -2380,9 +2455,11 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
     hipLaunchKernelGGL((rtk::trace_kernel<S, kSrcSmem, C, P, true, true, K>), dim3(4u * n_blocks), dim3(64), solo_lds, \
                        stream, *a)
     if (a->solo) {  // one wave per workgroup, no LDS image (the host clears the *_in_lds flags)
-        // one walk per kernel for the culled production shapes; others dispatch at run time
+        // one walk per kernel for the culled production shapes; others dispatch at run time.  The
+        // walk kernels take the short candidate square root unconditionally (trace_kernel kFastSqrt):
+        // a scene outside its proven r^2 range runs the run-time kernel, which keeps the IEEE one.
         if constexpr (P == 0 || P == 4 || P == 8 || P == 16) {
-            if (cull) {
+            if (cull && (a->fast_sqrt || !RTK_FAST_SQRT_KERNELS)) {
 #define RTK_WALKS(S)                                                          \
     switch (a->walk) {                                                        \
         case kWalkGroups: RTK_LAUNCH_SOLO(S, true, kWalkGroups); return;      \
