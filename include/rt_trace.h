@@ -171,7 +171,7 @@ typedef struct rt_device_options {
     int32_t Cull;                /* primary-ray cone cull and dead-tile fold (default on)            */
     int32_t Prefilter;           /* secondary-ray prefilter (default: per scene)                     */
     int32_t PrefilterRelative;   /* per-lane prefilter thresholds (default: per scene)               */
-    int32_t Clusters;            /* cluster walk (default: scenes of <= 64 groups; ON: any size)     */
+    int32_t Clusters;            /* cluster walk (default: scenes of <= 128 groups; ON: any size)    */
     int32_t ClusterCount;        /* k-means top clusters K >= 2 (0: ~1.25 sqrt(n) or n / 8..17)      */
     int32_t SubClusterSpheres;   /* spheres per sub-cluster of two-level tables (0: 3, per-lane 4)   */
     int32_t SecondaryThreshold;  /* lanes a secondary round waits for (0: 24/40/48 by walk size)     */
@@ -181,7 +181,8 @@ typedef struct rt_device_options {
     int32_t SphereSourceLds;     /* four-wave kernels read spheres from LDS, not SMEM (default off)  */
     int32_t SceneInHbm;          /* four-wave kernels keep the scene out of LDS (default off)        */
     int32_t TablesInLds;         /* four-wave kernels' rsqrt / fold tables in LDS at P <= 8 (on)     */
-    int32_t WalkAny;             /* the one-wave kernel picks its walk at run time (default off)     */
+    int32_t WalkAny;             /* the one-wave kernel picks its walk at run time (default off;     */
+                                 /* MaxBounce == 0 and r^2 outside the short sqrt's range always do) */
     int32_t Interleave;          /* wave tiles interleaved over the block tile (default off)         */
     int32_t MergeRounds;         /* primary + secondary rays in every round (default: <= 2 groups)   */
     int32_t TileOrder;           /* heaviest-first order learned from earlier launches (default on)  */
@@ -292,10 +293,24 @@ typedef struct rt_trace_info {
                                  pass's order (measuring tile costs), the rest
                                  heaviest-first; the same bits as one launch  */
     uint32_t OneWaveGroups;   /* 1: one wave per workgroup (no LDS image)    */
-    uint32_t Walk;            /* secondary walk compiled into the kernel: 0
-                                 run-time dispatch, 1 per-group loops, 2/3/4
-                                 cluster walk with 1/2/4 mask words, 5/6/7
-                                 the same with per-lane thresholds           */
+    uint32_t Walk;            /* the host's routing of the secondary walk
+                                 (one-wave launches; else 0): 0 run-time
+                                 dispatch, 1 per-group loops, 2/3/4 cluster
+                                 walk with 1/2/4 mask words, 5/6/7 the same
+                                 with per-lane thresholds.  1-7 run a kernel
+                                 compiled for that walk alone, which also
+                                 takes launch facts at compile time; a launch
+                                 without one of them is routed to 0, the
+                                 run-time kernel, which tests them:
+                                 MaxBounce >= 1 (MaxBounce == 0 -> 0), every
+                                 r^2 in the short square root's range (a scene
+                                 outside it -> 0), WalkAny off (on -> 0).
+                                 Walk kernels exist for the launch shapes
+                                 PixelsPerLane 4 and LanesPerPixel 4, 8, 16
+                                 with the primary cull: at LanesPerPixel 1, 2
+                                 or 32, or with Cull off, a routing of 1-7
+                                 still runs the run-time kernel, which
+                                 dispatches that same walk                    */
     uint32_t PixelsPerLane;   /* 4: each lane traced 4 pixels in turn (one-lane-
                                  per-pixel launches of one frame), else 1     */
     uint32_t PixelsSorted;    /* 1: the block tiles' pixels were dealt to their

@@ -1195,6 +1195,10 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     // (53 >= 2*24 + 2: double rounding is innocuous for division)
     a.inv_width = (float)(1.0 / (double)(float)desc->Width);
     a.inv_height = (float)(1.0 / (double)(float)desc->Height);
+    // the divisors themselves: the u32 -> f32 conversion (round to nearest even; exact here, sizes are
+    // at most 65536) the kernel otherwise repeats for every sample
+    a.width_f = (float)desc->Width;
+    a.height_f = (float)desc->Height;
     a.local_rows = local_rows;
     a.prev_count = desc->PreviousRayCount;
     a.frames = desc->Frames;
@@ -1226,6 +1230,7 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     a.merge_rounds = d->merge_env == 1 || (d->merge_env == -1 && d->n_groups[rs] <= kMergeGroups) ? 1u : 0u;
     // Round 5 (primary table, steady state): 24 for the small walks, against 16 / 32: C2 +1.2 %, C3 +1.0 %, the
     // 4-rank share -2.7 %, the 8-rank share -0.8 % (profiles/r05r_sec_threshold_ab.txt).
+    // (never 0 in the kernel, whose round decision compares the count of secondary lanes against it: round_select)
     a.sec_threshold = d->sec_threshold;
     if (a.sec_threshold == 0)
         a.sec_threshold = (a.clusters ? a.n_cpairs : a.n_groups) >= 12u ? (a.pf_relative ? 48u : 40u) : 24u;
@@ -1295,6 +1300,12 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
         // the walk kernels hold only the short candidate square root (rt_kernel.hip kFastSqrt): a scene
         // with an r^2 outside its proven range takes the run-time kernel and its IEEE square root
         if (!a.fast_sqrt) a.walk = kWalkAny;
+        // ... and they take the launch facts their trip loop would otherwise re-test at compile time
+        // (rt_kernel.hip kFacts): at least one bounce (a zero-bounce launch traces nothing and folds
+        // black: the run-time kernel keeps that path), at least one frame (Frames == 0 returned above,
+        // and no part of a split launch is empty) and, for the cluster walks, a table with at least
+        // one cluster-pair entry (a.clusters is set only with n_cpairs >= 1, above)
+        if (a.max_bounce == 0) a.walk = kWalkAny;
     }
     const int src = a.scene_in_lds ? d->src : kSrcSmem;  // a scene in HBM is read through the scalar cache
     const uint32_t n_tiles = rtk_tile_count(desc->Width, local_rows, lpp);
@@ -1376,7 +1387,8 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
                 // leading parts of head_samples, x split_growth, ... samples per lane
                 // while the rest keeps at least half the frames
                 uint32_t f = d->head_samples * lanes, used = 0;
-                for (uint32_t i = 0; i + 1 < d->split_parts && used + f <= desc->Frames / 2u; ++i) {
+                // (f != 0: an extreme SplitGrowth wraps the product; no part of a launch is empty)
+                for (uint32_t i = 0; i + 1 < d->split_parts && f != 0 && used + f <= desc->Frames / 2u; ++i) {
                     split[n_split++] = f;
                     used += f;
                     f *= d->split_growth;

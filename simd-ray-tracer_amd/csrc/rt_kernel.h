@@ -60,6 +60,7 @@ struct TraceArgs {
     float cam_pos[3], cam_x[3], cam_y[3], film_center[3];
     float film_w, film_h;
     float inv_width, inv_height;  // RN(1/(f32)width), RN(1/(f32)height)
+    float width_f, height_f;      // (f32)width, (f32)height: the divisors themselves (start_sample)
     uint32_t width, height, local_rows;
     uint32_t prev_count, frames, max_bounce;
     uint32_t n_groups, n_spheres, use_sky, flags;  // n_spheres: scalar rule set only

@@ -257,16 +257,24 @@ __device__ __forceinline__ cargs_t &kernel_args() {
     return *p;
 }
 
+// A launch-invariant value tested where it is used: opaque to the optimiser at that use, so the
+// test stays there as one scalar compare.  Left to the compiler the compare is hoisted out of
+// the trip loop and its result held across the loop as a 64-bit lane mask.
+__device__ __forceinline__ uint32_t at_use(uint32_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
 template <typename Args>
 __device__ __forceinline__ void start_sample(const Args &a, uint32_t x, uint32_t y, uint32_t frame, Sample &p) {
     p.rng = seed_mix(((uint64_t)frame * a.height + y) * a.width + x);
     const float jx = rand_float(p.rng, -0.5f, kInvRange1);
     const float jy = rand_float(p.rng, -0.5f, kInvRange1);
-    // ((x + Jx) * 2) / W with W's reciprocal RN(1/W) from the host: the
+    // ((x + Jx) * 2) / W with (f32)W and its reciprocal RN(1/W) from the host: the
     // numerator is +0 or >= 2^-24 (Jx = -0.5 + r is never -0), so div_rn's
     // range condition holds
-    const float fx = -1.0f + div_rn(((float)x + jx) * 2.0f, (float)a.width, a.inv_width);
-    const float fy = -1.0f + div_rn(((float)y + jy) * 2.0f, (float)a.height, a.inv_height);
+    const float fx = -1.0f + div_rn(((float)x + jx) * 2.0f, a.width_f, a.inv_width);
+    const float fy = -1.0f + div_rn(((float)y + jy) * 2.0f, a.height_f, a.inv_height);
     const float kx = (fx * a.film_w) * 0.5f;
     const float ky = (fy * a.film_h) * 0.5f;
     const float px = (a.film_center[0] + kx * a.cam_x[0]) + ky * a.cam_y[0];
@@ -660,6 +668,42 @@ __device__ __forceinline__ uint64_t ballot_and(bool a, bool b) {
     return __builtin_amdgcn_ballot_w64(a) & __builtin_amdgcn_ballot_w64(b);
 }
 
+// One trip's round decision (trace_kernel), on the scalar unit in six instructions:
+//   pri    = want & ring                   the lanes that can start their pending sample
+//   do_sec = popcount(sec) >= (pri ? thr : 1)
+//          = sec != 0 && (pri == 0 || popcount(sec) >= thr) for thr >= 1 (rt_host.cpp sets no 0)
+//   round  = do_sec ? sec : pri            the lanes this round traces
+// The conjunction's own SCC (pri != 0) picks the count to compare against and the compare's SCC
+// picks the round's mask (as merge_word1 does); the compiler's lowering turned each compare into
+// a 64-bit lane mask (s_cselect_b64 -1/0) and combined and re-tested the masks -- about 20
+// scalar instructions for the same three values.  do_sec comes back as an integer so that its
+// later tests are scalar compares of it, not further lane masks.
+__device__ __forceinline__ void round_select(uint64_t want, uint64_t ring, uint64_t sec, uint32_t thr, uint64_t &pri,
+                                             uint32_t &do_sec, uint64_t &round) {
+    uint32_t need;
+    asm("s_and_b64 %[pri], %[want], %[ring]\n\t"
+        "s_cselect_b32 %[need], %[thr], 1\n\t"
+        "s_bcnt1_i32_b64 %[ds], %[sec]\n\t"
+        "s_cmp_ge_u32 %[ds], %[need]\n\t"
+        "s_cselect_b32 %[ds], 1, 0\n\t"
+        "s_cselect_b64 %[rnd], %[sec], %[pri]"
+        : [pri] "=&s"(pri), [need] "=&s"(need), [ds] "=&s"(do_sec), [rnd] "=&s"(round)
+        : [want] "s"(want), [ring] "s"(ring), [sec] "s"(sec), [thr] "s"(thr)
+        : "scc");
+}
+
+// (a | b) != 0 as an integer from the OR's own SCC: the test of it is then one scalar compare
+__device__ __forceinline__ uint32_t any_lane(uint64_t a, uint64_t b) {
+    uint64_t t;
+    uint32_t r;
+    asm("s_or_b64 %[t], %[a], %[b]\n\t"
+        "s_cselect_b32 %[r], 1, 0"
+        : [t] "=&s"(t), [r] "=&s"(r)
+        : [a] "s"(a), [b] "s"(b)
+        : "scc");
+    return r;
+}
+
 // Entry e of the cluster table at byte offset off (a 32-bit offset from the
 // table's base keeps the per-entry address arithmetic to one SALU add).
 __device__ __forceinline__ cv4f_t *cl_entry(cv4f_t *ct, uint32_t off) {
@@ -949,7 +993,11 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         }
     };
     if (ps) ps->cl_tested += a.n_cpairs;
-    for (uint32_t off = 0, end = a.n_cpairs * kEntryBytes; off != end; off += kEntryBytes) {
+    // (every caller walks a table of at least one cluster-pair entry -- the run-time kernel tests
+    // n_cpairs, the walk kernels are launched with one only: no zero-trip test in front of the loop)
+    uint32_t off = 0;
+    const uint32_t end = a.n_cpairs * kEntryBytes;
+    do {
         cv4f_t *e = cl_entry(ct, off);
         uint64_t m0, m1;
         v4f_t r2;
@@ -965,7 +1013,8 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         } else {
             members(r2, m0 != 0, m1 != 0);
         }
-    }
+        off += kEntryBytes;
+    } while (off != end);
     cv4f_t *gp = (cv4f_t *)a.groups;
 #pragma unroll
     for (int w = 0; w < W; ++w) {
@@ -973,7 +1022,10 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         while (m) {
             const uint32_t q = (uint32_t)__builtin_ctzll(m) & ~1u;  // first pair of the lowest flagged group
             const uint32_t g = 32u * (uint32_t)w + (q >> 1);
-            const bool f01 = (m >> q) & 1u, f23 = (m >> (q + 1u)) & 1u;
+            // (both flags from one shift, each a 32-bit bit test; the 64-bit tests of bits q and q + 1
+            // cost a shift, a mask and a 64-bit compare apiece on the scalar unit)
+            const uint32_t pp = (uint32_t)(m >> q);
+            const bool f01 = (pp & 1u) != 0u, f23 = (pp & 2u) != 0u;
             m &= ~(3ull << q);
             if (ps) ps->pairs += (f01 ? 1u : 0u) + (f23 ? 1u : 0u);
             recheck_pairs<SIMD>(a, load_group_exact_at(gp + kGroupF4 * g), g, ray, h, fast, f01, f23);
@@ -1227,6 +1279,9 @@ constexpr int solo_waves(int walk) { return walk == kWalkCl2 ? RTK_SOLO_WAVES_CL
 #ifndef RTK_FAST_SQRT_KERNELS  // A/B: make variant KFLAGS=-DRTK_FAST_SQRT_KERNELS=0 (the flag tested at every site)
 #define RTK_FAST_SQRT_KERNELS 1
 #endif
+#ifndef RTK_LAUNCH_FACTS  // A/B: make variant KFLAGS=-DRTK_LAUNCH_FACTS=0 (every kernel tests the launch facts)
+#define RTK_LAUNCH_FACTS 1
+#endif
 template <int WALK> struct Walk {
     // the per-group walk (small scenes) may merge primary and secondary rounds
     static constexpr bool MERGEABLE = WALK == kWalkAny || WALK == kWalkGroups;
@@ -1267,6 +1322,21 @@ void trace_kernel(TraceArgs a) {
     // no flag test and no IEEE body at its candidate sites.  Every other kernel tests the flag.
     constexpr bool kFastSqrt = RTK_FAST_SQRT_KERNELS && SOLO && WALK != kWalkAny;
     const bool fast = kFastSqrt || a.fast_sqrt != 0u;
+    // Launch facts, by the same routing (rt_host.cpp, beside the fast_sqrt rule): a walk-specialised
+    // one-wave kernel runs only launches with max_bounce >= 1 and frames >= 1, and a cluster walk only
+    // with a table of at least one cluster-pair entry over at least one group.  Tested inside the trip
+    // loop these were lane masks held in SGPRs across it (four of them spilled to VGPR lanes); the
+    // run-time kernel (kWalkAny) keeps every test.
+    constexpr bool kFacts = RTK_LAUNCH_FACTS && SOLO && WALK != kWalkAny;
+    if constexpr (kFacts) {
+        __builtin_assume(a.max_bounce != 0u);
+        __builtin_assume(a.frames != 0u);
+        if constexpr (Walk<WALK>::CLUSTERS) {
+            __builtin_assume(a.n_cpairs != 0u);
+            __builtin_assume(a.n_groups != 0u);
+        }
+    }
+    const bool bounces = kFacts || a.max_bounce != 0u;  // (false: nothing is traced, every frame folds black)
     extern __shared__ float4 smem[];
     // first launch of a key: the host has not read the live-tile count back, so
     // the grid covers every tile (live first) and blocks past the count leave
@@ -1372,6 +1442,7 @@ void trace_kernel(TraceArgs a) {
     float4 *ring = s_ring + sw * kRing * kRingStride + pl;
 
     const uint32_t n_words = rtk_mask_words(a.n_groups);
+    if constexpr (kFacts && Walk<WALK>::CLUSTERS) __builtin_assume(n_words != 0u);  // (n_groups >= 1)
     // the wave tile's primary pair mask, from the cull pass (rtk_launch_cull)
     // (a permuted wave's pixels come from all four quadrants: the union of their masks)
     if (CULL)
@@ -1444,7 +1515,7 @@ void trace_kernel(TraceArgs a) {
     // sample's Out is exactly 0 (main.cpp:433-440), its one segment still
     // counts (main.cpp:390), and its blend is Final = 0*(1/n) + Prev*((n-1)/n)
     // = RN(Prev*((n-1)/n)) -- folded here without generating the rays.
-    bool empty_tile = CULL && !a.use_sky && a.max_bounce != 0;
+    bool empty_tile = CULL && !a.use_sky && bounces;
     if (CULL)
         for (uint32_t w = 0; w < n_words; ++w) empty_tile = empty_tile && s_maskw[w] == 0;
     // (an all-zero running mean stays exactly zero: nothing to fold)
@@ -1598,45 +1669,60 @@ void trace_kernel(TraceArgs a) {
         // the pixel's owner lane (first of its P-lane quad slice) via DPP
         uint32_t folded_g = fold_cursor();
         uint32_t want_n = 0;  // kDynamic: the slice's lanes wanting a sample
+        // The trip's lane masks, each predicate balloted once (the header runs on the CU's one scalar
+        // unit for every trip): want = the lanes whose next sample is pending, before the hand-out
+        // and after it (lanes past the last frame have left)
+        uint64_t want = __builtin_amdgcn_ballot_w64(mode == 0u);
         if (kDynamic) {
-            const uint32_t sw_bits = (uint32_t)((__builtin_amdgcn_ballot_w64(mode == 0u) >> slice_base) & ((1ull << LP) - 1ull));
+            const uint32_t sw_bits = (uint32_t)((want >> slice_base) & ((1ull << LP) - 1ull));
             want_n = __builtin_popcount(sw_bits);
             if (mode == 0u) {
                 k = next + __builtin_popcount(sw_bits & ((1u << j) - 1u));
                 if (k >= a.frames) mode = 2u;
             }
+            want = __builtin_amdgcn_ballot_w64(mode == 0u);
         }
         // (lane masks from single compares: see ballot_and)
         bool ring_ok = LP == 1 || k < folded_g + kRing;
         bool can_start = mode == 0u && ring_ok;
-        uint64_t pri = LP == 1 ? __builtin_amdgcn_ballot_w64(mode == 0u) : ballot_and(mode == 0u, ring_ok);
         const uint64_t sec = __builtin_amdgcn_ballot_w64(mode == 1u);
-        // (one lane per pixel folds each sample as it ends: nothing left to fold then)
-        const uint64_t alive = __builtin_amdgcn_ballot_w64(mode != 2u) |
-                               (LP > 1 ? folding & __builtin_amdgcn_ballot_w64(folded < a.frames) : 0ull);
-        if (alive == 0) break;
+        // (one lane per pixel folds each sample as it ends: nothing left to fold then); the fold
+        // cursors are looked at only once no lane has anything left to trace
+        if (any_lane(want, sec) == 0u && (LP == 1 || (folding & __builtin_amdgcn_ballot_w64(folded < a.frames)) == 0)) break;
         const uint64_t st_t0 = kStats && a.stats ? __builtin_amdgcn_s_memtime() : 0;
         // Secondary segments run the full sphere loop; let them gather until
         // enough lanes share one (or no primary work is ready).  Merged rounds
         // (scenes of one or two groups, TraceArgs.merge_rounds): every round
         // starts new samples AND continues paths, all through the exact loop.
         const bool merged = kMergeable && a.merge_rounds != 0u;
-        const bool do_sec = !merged && sec != 0 && (pri == 0 || __builtin_popcountll(sec) >= a.sec_threshold);
-        // (lazy: only when some lane waits for ring space, or nothing else is left)
-        const bool fold_now = !do_sec && ((pri | sec) == 0 || (__builtin_amdgcn_ballot_w64(mode == 0u) & ~pri) != 0);
-        if (fold_now) {
-            // the owners fold only before a primary round (or when nothing is left to
-            // trace): a secondary round starts no sample, so it needs no ring space
-            const uint64_t st_f0 = kStats && a.stats ? __builtin_amdgcn_s_memtime() : 0;
-            fold_ring();
-            if (kStats && a.stats) st_cyc_fold += __builtin_amdgcn_s_memtime() - st_f0;
-            folded_g = fold_cursor();
-            ring_ok = LP == 1 || k < folded_g + kRing;
-            can_start = mode == 0u && ring_ok;
-            pri = LP == 1 ? __builtin_amdgcn_ballot_w64(mode == 0u) : ballot_and(mode == 0u, ring_ok);
+        // pri = the lanes that can start their sample; do_sec = sec != 0 && (pri == 0 ||
+        // popcount(sec) >= sec_threshold); round = the lanes this round traces (round_select)
+        uint64_t pri, round;
+        uint32_t do_sec;
+        round_select(want, LP == 1 ? ~0ull : __builtin_amdgcn_ballot_w64(ring_ok), sec, a.sec_threshold, pri, do_sec, round);
+        if (merged) do_sec = 0u;
+        if (do_sec == 0u) {
+            // The owners fold only before a primary round: a secondary round starts no sample, so
+            // it needs no ring space.  Lazy: only when some lane waits for ring space (pri is a
+            // subset of want) or nothing is left to trace: pri | sec == 0.  With split rounds a
+            // primary round with pri == 0 has sec == 0 too (round_select), so pri alone is tested;
+            // merged rounds (do_sec forced to 0) keep paths going with no lane wanting a sample,
+            // and do not fold then.
+            if (want != pri || (kMergeable ? (pri | sec) == 0 : pri == 0)) {
+                const uint64_t st_f0 = kStats && a.stats ? __builtin_amdgcn_s_memtime() : 0;
+                fold_ring();
+                if (kStats && a.stats) st_cyc_fold += __builtin_amdgcn_s_memtime() - st_f0;
+                folded_g = fold_cursor();
+                ring_ok = LP == 1 || k < folded_g + kRing;
+                can_start = mode == 0u && ring_ok;
+                pri = LP == 1 ? want : want & __builtin_amdgcn_ballot_w64(ring_ok);
+            }
+            if (merged) pri |= sec;  // (the lanes a merged round traces)
+            round = pri;
+            // the slice's lanes that start now are its lowest-ranked wanting ones (none: no change)
+            if (kDynamic) next = min(next + want_n, min(a.frames, folded_g + kRing));
         }
-        if (merged) pri |= sec;  // (the lanes a merged round traces)
-        if ((pri | sec) != 0) {
+        if (round != 0) {  // (else: every lane is done and the fold above took the last parked samples)
             if (kStats && a.stats) {
                 if (do_sec) { st_sec_it += 1; st_sec_lanes += __builtin_popcountll(sec); }
                 if (do_sec && __builtin_popcountll(sec) < 16) { st_sparse_it += 1; st_sparse_lanes += __builtin_popcountll(sec); }
@@ -1656,18 +1742,12 @@ void trace_kernel(TraceArgs a) {
                     st_pri_done += __builtin_popcountll(__ballot(mode == 2u));
                 }
             }
-            // do_sec ? mode == 1 : can_start, as one compare against a uniform mode
-            // and a uniform override of the ring test (no lane-mask select)
-            const bool traces = merged ? (mode == 0u && ring_ok) || mode == 1u
-                                       : mode == (do_sec ? 1u : 0u) && (do_sec || ring_ok);
-            if (a.max_bounce != 0) nrays += __builtin_popcountll(do_sec ? sec : pri);
-            // the slice's lanes that start now are its lowest-ranked wanting ones
-            if (kDynamic && !do_sec) next = min(next + want_n, min(a.frames, folded_g + kRing));
-            if (traces) {
+            if (bounces) nrays += (uint32_t)__builtin_popcountll(round);
+            if (__builtin_amdgcn_inverse_ballot_w64(round)) {  // (the mask itself becomes exec)
                 pseg += 1u;
                 if (!do_sec && mode == 0u) start_sample(kernel_args(), x, y, a.prev_count + k, p);
                 bool done;
-                if (a.max_bounce == 0) {
+                if (!bounces) {
                     done = true;  // no segment is traced; the frame folds black
                 } else {
                     Hit h;
@@ -1760,7 +1840,7 @@ void trace_kernel(TraceArgs a) {
                         inside = h.ins != 0;
                     }
                     if (tmin == kFMax) {
-                        if (a.use_sky) {  // main.cpp:434-438
+                        if (at_use(a.use_sky)) {  // main.cpp:434-438
                             const float s = (p.ry.y + 1.0f) * 0.5f;
                             const float w = (1.0f - s) * 1.0f;
                             p.cx = p.cx + (w + s * 0.5f) * p.ax;
@@ -1774,9 +1854,9 @@ void trace_kernel(TraceArgs a) {
                     }
                 }
                 if (done) {
-                    const float ox = a.max_bounce == 0 ? 0.0f : p.cx;
-                    const float oy = a.max_bounce == 0 ? 0.0f : p.cy;
-                    const float oz = a.max_bounce == 0 ? 0.0f : p.cz;
+                    const float ox = bounces ? p.cx : 0.0f;
+                    const float oy = bounces ? p.cy : 0.0f;
+                    const float oz = bounces ? p.cz : 0.0f;
                     if (LP == 1) {
                         // ---- running-mean blend (main.cpp:484-489), in order by construction
                         const uint32_t pc = a.prev_count + k;
@@ -1825,10 +1905,7 @@ void trace_kernel(TraceArgs a) {
             }
         }
         const uint64_t st_t1 = kStats && a.stats ? __builtin_amdgcn_s_memtime() : 0;
-        if (kStats && a.stats && (pri | sec) != 0) {
-            const bool was_sec = sec != 0 && (pri == 0 || __builtin_popcountll(sec) >= a.sec_threshold);
-            (was_sec ? st_cyc_sec : st_cyc_pri) += st_t1 - st_t0;
-        }
+        if (kStats && a.stats && round != 0) (do_sec != 0u ? st_cyc_sec : st_cyc_pri) += st_t1 - st_t0;
     }
 
     if (FOLD3) {  // channels 1 and 2 from lanes j = 1, 2 of the pixel's quad (quad_perm 1,1,1,1 / 2,2,2,2)
@@ -2459,7 +2536,12 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
         // walk kernels take the short candidate square root unconditionally (trace_kernel kFastSqrt):
         // a scene outside its proven r^2 range runs the run-time kernel, which keeps the IEEE one.
         if constexpr (P == 0 || P == 4 || P == 8 || P == 16) {
-            if (cull && (a->fast_sqrt || !RTK_FAST_SQRT_KERNELS)) {
+            // (the launch facts of the walk kernels, trace_kernel kFacts: the host routes by them too;
+            // a launch without one of them runs the run-time kernel whatever a->walk says)
+            if (cull && (a->fast_sqrt || !RTK_FAST_SQRT_KERNELS) &&
+                ((a->max_bounce != 0u && a->frames != 0u &&
+                  (a->walk < (uint32_t)kWalkCl1 || (a->clusters != nullptr && a->n_cpairs != 0u && a->n_groups != 0u))) ||
+                 !RTK_LAUNCH_FACTS)) {
 #define RTK_WALKS(S)                                                          \
     switch (a->walk) {                                                        \
         case kWalkGroups: RTK_LAUNCH_SOLO(S, true, kWalkGroups); return;      \
