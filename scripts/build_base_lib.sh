@@ -16,7 +16,7 @@ else
   make -s -j8 -C "$tmp/simd-ray-tracer_amd" librt_trace.so
   cp "$tmp/simd-ray-tracer_amd/librt_trace.so" "$repo/simd-ray-tracer_amd/librt_trace_$name.so"
 fi
-# every symbol must resolve (a revision whose Makefile links no P = 16 object would leave rtk_launch_p16 undefined)
+# every symbol must resolve (a revision whose Makefile links no P = 16 object would leave rtk_launch_p16 undefined: rt_trace_p16.hip)
 if nm -D --undefined-only "$repo/simd-ray-tracer_amd/librt_trace_$name.so" | grep -q " rtk_"; then
   echo "librt_trace_$name.so has undefined rtk_ symbols" >&2; exit 1
 fi

@@ -34,7 +34,7 @@ def makespan(durations, slots):
 
 
 def bucket(c):
-    """Quarter-octave bucket of a cost (rt_kernel.hip tile_bucket, without the clamp)."""
+    """Quarter-octave bucket of a cost (rt_sched.hip tile_bucket, without the clamp)."""
     c = np.maximum(c, 1.0)
     l = np.floor(np.log2(c))
     frac = np.floor((c / 2.0 ** l - 1.0) * 4.0)

@@ -34,7 +34,7 @@ struct rt_device {
     uint32_t sec_threshold = 0;  // 0: per scene (rt_trace), else rt_device_options SecondaryThreshold
     int prefilter_env = -1;  // options Prefilter: -1 auto, 0 off, 1 on
     uint32_t prefilter[2] = {0, 0};  // per rule set, decided at upload
-    uint32_t pf_relative[2] = {0, 0};  // per rule set: the threshold row holds r^2, per-lane thresholds (rt_kernel.hip kPfRel)
+    uint32_t pf_relative[2] = {0, 0};  // per rule set: the threshold row holds r^2, per-lane thresholds (rtk_walk.h kPfRel)
     int pf_rel_env = -1;  // options PrefilterRelative: -1 auto (where the scene-wide bound does not pay), 0 never, 1 always
     uint32_t fast_sqrt[2] = {0, 0};  // per rule set: candidate sqrt in sqrt_rn's verified range
     float4 *d_clusters[2] = {nullptr, nullptr};  // clustered prefilter tables (cluster_table)
@@ -413,7 +413,7 @@ static void put_material(float *dst, const rt_material &m) {
 }
 
 // Prefilter thresholds r2p (row 4 of each group) for the secondary-ray
-// sphere loop (rt_kernel.hip, pair_prefilter).  Secondary origins are hit
+// sphere loop (rtk_walk.h, pair_prefilter).  Secondary origins are hit
 // points, i.e. lie within |r_i| of a hittable sphere centre s_i, so
 //   M_j = (max_i |s_i - s_j| + |r_i|)^2   (with slack for origin rounding)
 // bounds |C|^2 for sphere j, and r2p_j = r^2_j + M_j (32u + 1.01K) rounded
@@ -483,7 +483,7 @@ static bool prefilter_rows(std::vector<float> &gv, uint32_t n_groups, bool simd)
 //
 // relative (the per-lane thresholds of pack_set, where the scene-wide M makes
 // the bound above useless): the thresholds are formed per lane from the lane's
-// own cc = |Q|^2 (rt_kernel.hip kClRel / kPfRel / kBehindRel).  With A_j =
+// own cc = |Q|^2 (rtk_walk.h kClRel / kPfRel / kBehindRel).  With A_j =
 // |Q|(1+u) + delta_j >= |C_j| (delta_j = |s_j - q_c|) the chain above reads
 //   sqrt(l(O+Q)) > delta_j + sqrt(r_j^2 + 13.3u A_j^2) + 2u A_j + u|Q|
 // and sqrt(r^2 + 13.3u A^2) <= r + sqrt(13.3u) A, so it holds when
@@ -546,7 +546,7 @@ static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, s
     // at K 40: 19.6k); C5 at 512 spp K/S = 32/4, 24/3, 28/3, 24/2 -> 47.4k/48.2k/
     // 48.3k/48.3k (one level: 46.3k).
     // two levels for tables of two or more mask words only: the kernel walks
-    // one-word tables (at most 32 groups) as one level (rt_kernel.hip clustered_groups)
+    // one-word tables (at most 32 groups) as one level (rtk_walk.h clustered_groups)
     const bool two_levels = *words >= 2u;
     const uint32_t div = two_levels ? (relative ? 17u : 10u) : (relative ? 12u : 8u);
     uint32_t k = std::max(2u, std::max((uint32_t)std::lround(1.25 * std::sqrt((double)n)), n / div));
@@ -923,7 +923,7 @@ static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env 
     p.fast_sqrt = sqrt_range_ok(gv, n, rs == 0);
     // Where the scene-wide bound M_j makes r2p useless (a huge sphere: RTWeekend's
     // ground), the thresholds are formed per lane from the lane's own |C|^2 instead
-    // (rt_kernel.hip kPfRel, kClRel): the cluster table is built for that rule, and
+    // (rtk_walk.h kPfRel, kClRel): the cluster table is built for that rule, and
     // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
     p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
     p.n_cpairs = cluster_table(gv, n, p.clusters, &p.cl_words, p.relative, &p.cl_levels, &p.cl_sub_pairs, cluster_k,
@@ -1254,7 +1254,7 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
         while (lpp > 1 && (uint32_t)lpp / 2u >= desc->Frames) lpp /= 2;
     }
     // One lane per pixel, and one frame (the reference's OnRender unit): each lane
-    // takes kPixelsPerLane pixels in turn (launch shape 0, rt_kernel.hip Shape<0>),
+    // takes kPixelsPerLane pixels in turn (launch shape 0, rtk_shape.h Shape<0>),
     // so a wave stays full after its first pass and the launch has a quarter of
     // the waves.  Measured on the 1080p OnRender frame: see DESIGN.md §6a.
     const uint32_t pixels_per_lane =
@@ -1292,20 +1292,9 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     if (d->solo_env && d->src == kSrcSmem) {  // one-wave workgroups keep no LDS image
         a.solo = 1u;
         a.lut_in_lds = a.fold_in_lds = a.scene_in_lds = 0u;
-        if (!a.clusters) a.walk = kWalkGroups;
-        else if (a.cl_words == 1u) a.walk = a.pf_relative ? kWalkCl1Rel : kWalkCl1;
-        else if (a.cl_words == 2u) a.walk = a.pf_relative ? kWalkCl2Rel : kWalkCl2;
-        else a.walk = a.pf_relative ? kWalkCl4Rel : kWalkCl4;
-        if (d->walk_any_env) a.walk = kWalkAny;
-        // the walk kernels hold only the short candidate square root (rt_kernel.hip kFastSqrt): a scene
-        // with an r^2 outside its proven range takes the run-time kernel and its IEEE square root
-        if (!a.fast_sqrt) a.walk = kWalkAny;
-        // ... and they take the launch facts their trip loop would otherwise re-test at compile time
-        // (rt_kernel.hip kFacts): at least one bounce (a zero-bounce launch traces nothing and folds
-        // black: the run-time kernel keeps that path), at least one frame (Frames == 0 returned above,
-        // and no part of a split launch is empty) and, for the cluster walks, a table with at least
-        // one cluster-pair entry (a.clusters is set only with n_cpairs >= 1, above)
-        if (a.max_bounce == 0) a.walk = kWalkAny;
+        // the walk-specialised kernel this launch asks for, or the run-time one (rt_kernel.h, the routing
+        // rule: a.clusters is set only with n_cpairs >= 1, above, and Frames == 0 returned above)
+        a.walk = rtk_walk_request(a, d->walk_any_env != 0);
     }
     const int src = a.scene_in_lds ? d->src : kSrcSmem;  // a scene in HBM is read through the scalar cache
     const uint32_t n_tiles = rtk_tile_count(desc->Width, local_rows, lpp);

@@ -1,5 +1,5 @@
 // rt_kernel.h — launch contract between the C-ABI host (rt_host.cpp) and the
-// gfx950 trace kernel (rt_kernel.hip).  Internal; not part of include/.
+// gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_sched.hip).  Internal; not part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -27,7 +27,7 @@ enum { kFlagAccumZero = 1, kFlagSrgbPow = 2 };
 // merges a flagged member into every word with one select and one OR each.
 // With pf_relative the thresholds are per lane: rc2p / r2p hold R_c / r^2 and
 // b the M-free behind bases (rt_host.cpp cluster_table, "relative"), and a
-// cluster pair also carries its height-slab bound (rt_kernel.hip slab test):
+// cluster pair also carries its height-slab bound (rtk_walk.h cluster_slab):
 //   row 3 = {b0 b1 srho0 srho1}, row 4 = {ymid0 ymid1 yhalf0 yhalf1}
 // (entries then have at least 5 rows; member entries leave row 4 to the bits).
 // padding members: threshold -inf, bits 0.
@@ -81,7 +81,7 @@ struct TraceArgs {
     uint32_t lut_in_lds;         // rsqrt table in the LDS image (else read from HBM: rtk_lut_in_lds)
     uint32_t fold_in_lds;        // running-mean weight table in the LDS image (else computed: rtk_fold_in_lds)
     uint32_t scene_in_lds;       // groups + materials copied into the LDS image (else read from HBM: GS kernels)
-    uint32_t pf_relative;        // prefilter: row kRowR2P holds r^2 and the threshold is per lane (rt_kernel.hip kPfRel)
+    uint32_t pf_relative;        // prefilter: row kRowR2P holds r^2 and the threshold is per lane (rtk_walk.h kPfRel)
     uint32_t solo;               // one wave per workgroup (4 x tiles workgroups of 64 threads; needs no LDS image)
     uint32_t walk;               // kWalk*: the one-wave kernel specialised for this launch's secondary walk
     // optional: live block tiles of the cull pass, on the device (kCullTotals).  Set while the host
@@ -128,10 +128,51 @@ constexpr uint32_t kMergeGroups = 2;
 // (live tiles, dead pixels), summed on the device after the pass.
 constexpr uint32_t kCullCounterWords = 132;
 constexpr uint32_t kCullTotals = 128;
-// Secondary-ray walk variants (rt_kernel.hip Walk<>): any (run-time dispatch),
+// Secondary-ray walk variants (rtk_shape.h Walk<>): any (run-time dispatch),
 // the per-group loops, or a cluster walk with 1/2/4 pair-mask words and
 // scene-wide or per-lane ("Rel") thresholds
 enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWalkCl2Rel, kWalkCl4Rel };
+
+// ---- Routing of the walk-specialised one-wave kernels (trace_kernel<..., SOLO = true, WALK != kWalkAny>).
+// Such a kernel holds one secondary walk and takes these facts of its launch at compile time
+// (rtk_trace.h trace_kernel, kFastSqrt and kFacts); a launch without one of them computes garbage
+// in it, so every launch goes through the two functions below and nothing else decides:
+//   fast_sqrt       every hittable r^2 is 0 or in [2^-36, 2^60], so a candidate's r^2 - dist is 0
+//                   or inside sqrt_rn's verified range [2^-60, 2^60]: the walk kernels hold the
+//                   short square root alone, the run-time kernel keeps the IEEE one beside it
+//   max_bounce >= 1 the walk kernels hold no zero-bounce path (such a launch traces nothing and
+//                   folds every frame black: the run-time kernel keeps that path)
+//   frames >= 1     (rt_trace returns before the launch at Frames == 0, and no part of a split
+//                   launch is empty)
+//   cluster walks   run only with a non-empty table over a non-empty scene: clusters set,
+//                   n_cpairs >= 1, n_groups >= 1 (their top loop has no zero-trip test), and with the
+//                   prefilter on (they do not test it; rt_trace sets clusters only with it)
+// and the kernels exist only for the culled production shapes (rtk_walk_shape).  Every other launch
+// runs the run-time kernel (kWalkAny), which tests each fact where it matters and dispatches the
+// walk the table asks for.
+// The walk rt_trace asks for (TraceArgs.walk, rt_trace_info.Walk) of a one-wave launch, from the
+// scene's table and the facts the host decides by; walk_any: rt_device_options WalkAny.
+static inline uint32_t rtk_walk_request(const TraceArgs &a, bool walk_any) {
+    if (walk_any || !a.fast_sqrt || a.max_bounce == 0u) return kWalkAny;
+    if (!a.clusters) return kWalkGroups;
+    if (a.cl_words == 1u) return a.pf_relative ? kWalkCl1Rel : kWalkCl1;
+    if (a.cl_words == 2u) return a.pf_relative ? kWalkCl2Rel : kWalkCl2;
+    return a.pf_relative ? kWalkCl4Rel : kWalkCl4;
+}
+// the launch shapes (lanes per pixel; 0: kPixelsPerLane pixels per lane) with walk kernels
+constexpr bool rtk_walk_shape(int lanes_per_pixel) {
+    return lanes_per_pixel == 0 || lanes_per_pixel == 4 || lanes_per_pixel == 8 || lanes_per_pixel == 16;
+}
+// The WALK template value of the kernel a launch runs: the request, when the launch has every fact
+// above (all tested here, whatever the request was derived from), else kWalkAny.
+static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_per_pixel) {
+    if (!a.solo || !rtk_walk_shape(lanes_per_pixel) || !cull) return kWalkAny;
+    if (!a.fast_sqrt || a.max_bounce == 0u || a.frames == 0u) return kWalkAny;
+    if (a.walk >= (uint32_t)kWalkCl1 && (a.clusters == nullptr || a.n_cpairs == 0u || a.n_groups == 0u || !a.prefilter))
+        return kWalkAny;
+    return a.walk <= (uint32_t)kWalkCl4Rel ? a.walk : (uint32_t)kWalkAny;
+}
+
 enum { kStatPriIters = 0, kStatPriLanes, kStatSecIters, kStatSecLanes, kStatPriGroups, kStatSecHitGroups,
        kStatSecSparseIters, kStatSecSparseLanes, kStatSecTailIters, kStatPriCycles, kStatSecCycles, kStatFoldCycles,
        kStatSetupCycles, kStatCullCycles, kStatSyncCycles, kStatPostCycles, kStatPfRounds, kStatPfGroups,
@@ -177,7 +218,7 @@ extern "C" int rtk_launch_tile_sort(uint32_t *cost, uint32_t *order, uint32_t *s
 // One-wave kernels' wave order: the live prefix (4 x live_tiles[0] units) of a sorted
 // order_in partitioned stably by XCD group (every eighth live tile by its heaviest
 // wave's rank) and interleaved so that every wave of a block tile runs on one XCD
-// (rt_kernel.hip, "XCD grouping"); the rest copied.  scratch: rtk_tile_sort_scratch(
+// (rt_sched.hip, "XCD grouping"); the rest copied.  scratch: rtk_tile_sort_scratch(
 // n_units) bytes (8 n_blk + 9 words used); aux: 2 x n_units / 4 words.
 extern "C" int rtk_launch_xcd_group(const uint32_t *order_in, uint32_t *order_out, uint32_t n_units,
                                     const unsigned long long *live_tiles, uint32_t *scratch, uint32_t *aux,

@@ -1,0 +1,729 @@
+// rt_sched.hip — the kernels around the trace launch: the primary-ray cull
+// pass, dead-tile fold, primary group rows, pixel sort, heaviest-first tile
+// sort, XCD grouping, RGBA8 encode, ray-counter sum and band assembly, with
+// their launchers and the tile geometry queries.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_kernel.h"
+#include "rtk_math.h"
+#include "rtk_shape.h"
+
+namespace rtk {
+
+// Conservative per-wave culling for primary rays.  All primary rays of a
+// tile start at CameraPosition and point into the tile's film rectangle
+// (+-0.5 px jitter), i.e. inside a cone (axis A, half-angle theta).  A sphere
+// can pass the exact test d < r^2 only if the LINE through the camera along
+// some cone direction comes within r of its centre, i.e. if the angle between
+// +-C and A is below theta + asin(r/|C|).  The cone and the test are computed
+// in f64, so their own rounding is negligible; the margins cover the f32 path
+// the kernel actually traces: each traced direction lies within ~1e-6 rad of
+// the ideal cone (film point and Normalize rounding; |jitter| <= 0.5 + 1e-7 px,
+// covered by the 0.501 px bound), and the reference-rounded distance is within
+// 13.3u|C|^2 of the exact one -- the test uses a 1e-5 rad
+// angular margin and r'^2 = r^2 (1 + 1e-5) + 1e-5 |C|^2, ten times both.  A
+// group it rejects is one every lane's exact test misses: skipping it changes
+// nothing.
+struct Cone {
+    double ax, ay, az;     // axis
+    double cos_t, sin_t;   // inflated half-angle
+};
+
+__device__ __forceinline__ Cone tile_cone(const TraceArgs &a, double u0, double u1, double v0, double v1) {
+    const double fcx = (double)a.film_center[0] - a.cam_pos[0];
+    const double fcy = (double)a.film_center[1] - a.cam_pos[1];
+    const double fcz = (double)a.film_center[2] - a.cam_pos[2];
+    const double aa[2] = {(-1.0 + (u0 * 2.0) / a.width) * a.film_w * 0.5, (-1.0 + (u1 * 2.0) / a.width) * a.film_w * 0.5};
+    const double bb[2] = {(-1.0 + (v0 * 2.0) / a.height) * a.film_h * 0.5,
+                          (-1.0 + (v1 * 2.0) / a.height) * a.film_h * 0.5};
+    double cx[4], cy[4], cz[4];
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const double ka = aa[i & 1], kb = bb[i >> 1];
+        const double x = fcx + ka * a.cam_x[0] + kb * a.cam_y[0];
+        const double y = fcy + ka * a.cam_x[1] + kb * a.cam_y[1];
+        const double z = fcz + ka * a.cam_x[2] + kb * a.cam_y[2];
+        const double inv = 1.0 / __builtin_sqrt(x * x + y * y + z * z);
+        cx[i] = x * inv;
+        cy[i] = y * inv;
+        cz[i] = z * inv;
+        sx += cx[i];
+        sy += cy[i];
+        sz += cz[i];
+    }
+    Cone c;
+    const double inv = 1.0 / __builtin_sqrt(sx * sx + sy * sy + sz * sz);
+    c.ax = sx * inv;
+    c.ay = sy * inv;
+    c.az = sz * inv;
+    double ct = 1.0;
+    for (int i = 0; i < 4; ++i) ct = fmin(ct, c.ax * cx[i] + c.ay * cy[i] + c.az * cz[i]);
+    const double st = __builtin_sqrt(fmax(0.0, 1.0 - ct * ct));
+    const double cd = 0.99999999995, sd = 1e-5;  // cos/sin of the 1e-5 rad margin
+    c.cos_t = ct * cd - st * sd;
+    c.sin_t = st * cd + ct * sd;
+    return c;
+}
+
+__device__ __forceinline__ bool cone_may_hit(const TraceArgs &a, const Cone &c, float px, float py, float pz, float r2) {
+    if (!(r2 >= 0.0f)) return false;  // padding lanes of the scalar packing (-inf)
+    const double qx = (double)px - a.cam_pos[0], qy = (double)py - a.cam_pos[1], qz = (double)pz - a.cam_pos[2];
+    const double c2 = qx * qx + qy * qy + qz * qz;
+    const double rr = (double)r2 * (1.0 + 1e-5) + 1e-5 * c2;
+    if (rr >= c2) return true;  // the camera is (nearly) inside: never cull
+    const double sb = __builtin_sqrt(rr / c2), cb = __builtin_sqrt(1.0 - rr / c2);
+    if (c.cos_t <= 0.0) return true;  // cone wider than 90 degrees: no culling
+    const double cos_lim = c.cos_t * cb - c.sin_t * sb;  // cos(theta + beta)
+    const double cos_phi = fabs(c.ax * qx + c.ay * qy + c.az * qz) / __builtin_sqrt(c2);
+    return cos_phi >= cos_lim - 1e-12;
+}
+
+// Primary-ray culling of one wave tile (TW x TH pixels at x0, ly0): bit p of
+// the mask is set when some sphere of pair p (sphere slots 2p, 2p + 1: half
+// p & 1 of group p >> 1) may pass some primary ray's exact test
+// (cone_may_hit).  One sphere per lane, 64 per ballot, folded into one bit
+// per pair; word w covers pairs 64w .. 64w+63 (spheres 128w .. 128w+127).
+template <int P>
+__device__ __forceinline__ uint64_t wave_tile_mask(const TraceArgs &a, const Cone &c, uint32_t w, uint32_t lane) {
+    const float *gf = reinterpret_cast<const float *>(a.groups);
+    uint64_t gm = 0;
+    for (uint32_t q = 0; q < 2u && w * 128u + q * 64u < 4u * a.n_groups; ++q) {
+        const uint32_t sph = w * 128u + q * 64u + lane;  // sphere slot 4*g + l
+        bool cand = false;
+        if (sph < 4u * a.n_groups) {
+            const float *row = gf + (size_t)(sph >> 2) * (4u * kGroupF4) + (sph & 3u);
+            cand = cone_may_hit(a, c, row[4u * kRowX], row[4u * kRowY], row[4u * kRowZ], row[4u * kRowR2]);
+        }
+        uint64_t m = __ballot(cand);
+        m = (m | (m >> 1)) & 0x5555555555555555ull;  // bit 2i: some sphere of pair 32q + i
+        m = (m | (m >> 1)) & 0x3333333333333333ull;  // compress the even bits into bits 0..31
+        m = (m | (m >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+        m = (m | (m >> 4)) & 0x00FF00FF00FF00FFull;
+        m = (m | (m >> 8)) & 0x0000FFFF0000FFFFull;
+        m = (m | (m >> 16)) & 0x00000000FFFFFFFFull;
+        gm |= m << (32u * q);
+    }
+    return gm;
+}
+
+// Striped launch counters of the cull pass (one atomic per block tile, spread
+// over kCullStripes addresses so they do not serialise on one): [0, 64) live
+// block tiles, [64, 128) image pixels of dead block tiles.
+constexpr uint32_t kCullStripes = 64;
+
+// The cull pass: one block per block tile, one wave per wave tile (the trace
+// kernel's geometry).  Runs once per camera / scene / launch geometry; the
+// trace launches reuse its masks and live-tile list.
+template <int P>
+__global__ __launch_bounds__(256) void cull_kernel(TraceArgs a, uint32_t *live, uint32_t *cost,
+                                                   unsigned long long *counters, uint32_t empty_capable) {
+    constexpr uint32_t TW = Shape<P>::TW, TH = Shape<P>::TH;
+    __shared__ uint32_t s_any;
+    const uint32_t tile = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
+    // the wave tile's pixel extent [x0, x1] x [ly0, ly1] (see trace_kernel)
+    const uint32_t x0 = tile_x * (2u * TW) + (a.interleave ? (wave & 1u) : (wave & 1u) * TW);
+    const uint32_t ly0 = tile_y * (2u * TH) + (a.interleave ? (wave >> 1) : (wave >> 1) * TH);
+    const uint32_t x1 = x0 + (a.interleave ? 2u : 1u) * (TW - 1u), ly1 = ly0 + (a.interleave ? 2u : 1u) * (TH - 1u);
+    if (threadIdx.x == 0) s_any = 0;
+    __syncthreads();
+    // the image rows of the wave tile's first and last band-local rows: the band
+    // map is increasing, so every row of the tile lies between them (a tile of
+    // 16 rows may span two 8-row bands, whose rows between are other devices':
+    // the cone then covers them too, which only makes it wider)
+    const uint32_t y0 = ((ly0 / a.band_rows) * a.band_count + a.band_index) * a.band_rows + ly0 % a.band_rows;
+    const uint32_t y1 = ((ly1 / a.band_rows) * a.band_count + a.band_index) * a.band_rows + ly1 % a.band_rows;
+    const Cone c = tile_cone(a, (double)x0 - 0.501, (double)x1 + 0.501, (double)y0 - 0.501, (double)y1 + 0.501);
+    const uint32_t n_words = rtk_mask_words(a.n_groups);
+    bool any = false;
+    for (uint32_t w = 0; w < n_words; ++w) {
+        const uint64_t gm = wave_tile_mask<P>(a, c, w, lane);
+        if (lane == 0) const_cast<uint64_t *>(a.masks)[((size_t)tile * 4u + wave) * n_words + w] = gm;
+        any = any || gm != 0;
+    }
+    // a wave tile entirely outside the image does no work
+    if (lane == 0 && any && x0 < a.width && ly0 < a.local_rows) atomicOr(&s_any, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool l = s_any != 0 || !empty_capable;
+        live[tile] = l ? 1u : 0u;
+        if (a.unit_waves) {  // the one-wave kernels' order ranks waves (4 * tile + quadrant)
+            for (uint32_t w = 0; w < 4u; ++w) cost[4u * tile + w] = l ? 2u : 0u;
+        } else {
+            cost[tile] = l ? 2u : 0u;
+        }
+        const uint32_t stripe = tile % kCullStripes;
+        if (l) {
+            atomicAdd(counters + stripe, 1ull);
+        } else {
+            const uint32_t bx = tile_x * 2u * TW, by = tile_y * 2u * TH;
+            const uint32_t w = min(2u * TW, a.width - bx), h = min(2u * TH, a.local_rows - by);
+            atomicAdd(counters + kCullStripes + stripe, (unsigned long long)w * h);
+        }
+    }
+}
+
+// The cull pass's striped counters summed on the device (one wave), so no
+// launch needs the host to read them: counters[kCullTotals] = live block
+// tiles, counters[kCullTotals + 1] = image pixels of dead block tiles.
+__global__ __launch_bounds__(64) void cull_total_kernel(unsigned long long *counters) {
+    const uint32_t lane = threadIdx.x;
+    unsigned long long live = counters[lane], dead = counters[kCullStripes + lane];
+    for (int off = 32; off > 0; off >>= 1) {
+        live += __shfl_xor(live, off);
+        dead += __shfl_xor(dead, off);
+    }
+    if (lane == 0) {
+        counters[kCullTotals] = live;
+        counters[kCullTotals + 1] = dead;
+    }
+}
+
+
+// Pixels of dead block tiles: no sphere group passes any of the tile's
+// (conservative) cone tests, so every primary ray of every sample misses;
+// without a sky term each sample's Out is exactly 0 (main.cpp:433-440), its
+// one segment still counts (main.cpp:390; dead pixels x frames, the pixels
+// from the cull pass's device total, added once), and its blend is
+// Final = 0*(1/n) + Prev*((n-1)/n) = RN(Prev*((n-1)/n)) -- folded here without
+// generating the rays (an all-zero running mean stays exactly zero).  The
+// ratios are the trace kernel's fold-table values.
+template <int P>
+__global__ __launch_bounds__(256) void empty_kernel(TraceArgs a, const uint32_t *live,
+                                                    const unsigned long long *dead_pixels) {
+    constexpr uint32_t BW = 2u * Shape<P>::TW, BH = 2u * Shape<P>::TH;
+    __shared__ float ratio[kFoldTable];
+    const bool fold = a.prev_count > 0 && !(a.flags & kFlagAccumZero);
+    if (fold)
+        for (uint32_t i = threadIdx.x; i < kFoldTable; i += blockDim.x) {
+            const uint32_t pc = a.prev_count + i;
+            ratio[i] = (float)pc / (float)(pc + 1u);
+        }
+    __syncthreads();
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        const unsigned long long dead_rays = *dead_pixels * a.frames;
+        if (dead_rays) atomicAdd(a.rays, dead_rays);
+    }
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, ly = blockIdx.y;
+    if (!(x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == 0u)) return;
+    const size_t pix = (size_t)ly * a.width + x;
+    float accx = 0.0f, accy = 0.0f, accz = 0.0f;
+    if (fold) {
+        const float4 pv = a.prev[pix];
+        accx = pv.x;
+        accy = pv.y;
+        accz = pv.z;
+    }
+    if (accx != 0.0f || accy != 0.0f || accz != 0.0f) {
+        for (uint32_t q = 0; q < a.frames; ++q) {
+            float r;
+            if (q < kFoldTable) {
+                r = ratio[q];
+            } else {
+                const uint32_t pc = a.prev_count + q;
+                r = (float)pc / (float)(pc + 1u);
+            }
+            accx = 0.0f + accx * r;
+            accy = 0.0f + accy * r;
+            accz = 0.0f + accz * r;
+        }
+    }
+    a.prev[pix] = make_float4(accx, accy, accz, 1.0f);
+    if (!a.skip_cur) a.cur[pix] = rgba8(accx, accy, accz, (a.flags & kFlagSrgbPow) != 0u);
+}
+
+// One wave per block tile: rank its pixels by the last launch's cost (ties by
+// index), so wave w of the next launch gets ranks [NPIX w, NPIX (w + 1)).
+// With pix_seg = S > 1 the ranked units are row segments of S pixels (summed
+// cost), dealt whole: a wave's pixels then form S-pixel runs of a row.
+template <int P>
+__global__ __launch_bounds__(64) void pixel_sort_kernel(TraceArgs a, uint8_t *perm) {
+    constexpr uint32_t TW = Shape<P>::TW, TH = Shape<P>::TH, BW = 2u * TW, NB = 4u * TW * TH;
+    static_assert(NB <= 64, "a block tile's pixels fit one wave");
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const uint32_t tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
+    uint8_t *pp = perm + (size_t)tile * 64u;
+    // a quadrant without candidate groups folds without tracing: keep such blocks as they are
+    if (a.masks) {
+        const uint32_t n_words = rtk_mask_words(a.n_groups);
+        bool live = false;
+        for (uint32_t w = 0; lane < 4u && w < n_words; ++w) live = live || a.masks[((size_t)tile * 4u + lane) * n_words + w] != 0;
+        if (__builtin_popcountll(__ballot(lane < 4u && live)) != 4) {
+            if (lane == 0) pp[0] = 0xFFu;
+            return;
+        }
+    }
+    uint32_t c = 0;
+    if (lane < NB) {
+        const uint32_t x = tile_x * BW + lane % BW, ly = tile_y * (2u * TH) + lane / BW;
+        c = x < a.width && ly < a.local_rows ? a.pix_cost[(size_t)ly * a.width + x] : 0u;
+    }
+    // segment size: a power of two dividing the block row (BW) and the wave's pixels
+    constexpr uint32_t NPIX = NB / 4u;
+    const uint32_t S = a.pix_seg >= 4u && NPIX >= 4u && BW % 4u == 0 ? 4u : a.pix_seg >= 2u && NPIX >= 2u ? 2u : 1u;
+    for (uint32_t off = 1; off < S; off <<= 1) c += (uint32_t)__shfl_xor((int)c, (int)off, 64);  // (every lane active)
+    const uint32_t seg = lane / S, nseg = NB / S;
+    uint32_t rank = 0;
+    for (uint32_t i = 0; i < nseg; ++i) {
+        const uint32_t ci = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)(i * S));
+        rank += ci < c || (ci == c && i < seg) ? 1u : 0u;
+    }
+    if (lane < NB) pp[rank * S + lane % S] = (uint8_t)lane;
+}
+
+// Scatter RCCL-gathered compact band images into the full framebuffer.
+__global__ __launch_bounds__(256) void assemble_kernel(const uint8_t *src, uint64_t rank_stride, uint8_t *dst,
+                                                       uint32_t width, uint32_t height, uint32_t elem,
+                                                       uint32_t band_rows, uint32_t band_count) {
+    const uint32_t y = blockIdx.y;
+    const uint32_t band = y / band_rows;
+    const uint32_t owner = band % band_count;
+    const uint32_t ly = (band / band_count) * band_rows + y % band_rows;
+    const uint8_t *s = src + owner * rank_stride + (uint64_t)ly * width * elem;
+    uint8_t *d = dst + (uint64_t)y * width * elem;
+    const uint32_t row_bytes = width * elem;
+    if ((row_bytes & 15u) == 0 && (((uintptr_t)s | (uintptr_t)d) & 15u) == 0) {
+        const uint4 *s4 = reinterpret_cast<const uint4 *>(s);
+        uint4 *d4 = reinterpret_cast<uint4 *>(d);
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < row_bytes / 16u; i += gridDim.x * blockDim.x)
+            d4[i] = s4[i];
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < row_bytes; i += gridDim.x * blockDim.x)
+            d[i] = s[i];
+    }
+}
+
+// ---- heaviest-first tile order for the next launch (counting sort of the
+// per-tile costs this launch measured into 32 log2 buckets, descending)
+// Counting sort of the tiles by log2(cost), heaviest bucket first, stable,
+// without atomics, over the whole grid (a single-block version was latency
+// bound at ~60 us; grid-wide device atomics on the few busy buckets ~300 us).
+// A wave walks its 64 tiles visiting only the distinct buckets present
+// (readlane of the first pending lane + ballot) and keeps per-bucket counters
+// in lane k of one VGPR.  Blocks cover 1024 tiles:
+//   tile_count_kernel: block j's kSortBuckets bucket counts -> bcount[kSortBuckets*j + k]
+//   tile_scan_kernel:  exclusive scan in (bucket descending, block ascending)
+//                      order, staged through LDS
+//   tile_rank_kernel:  per-wave bases inside the block, the walk again ->
+//                      order[rank] = tile
+// Consecutive ranks keep similar cost: blocks are dealt round-robin to the 8
+// XCDs, so alternating heavy and light tiles would put all heavy work on half
+// of them (measured 2x slower).
+constexpr uint32_t kSortBlock = 1024, kSortWaves = kSortBlock / 64, kScanLds = 16384;
+constexpr uint32_t kSortBuckets = 64;  // one counter per lane
+
+// Quarter-octave buckets of the cost (cycles): 4 log2(c) + the two bits after
+// the leading one, offset so octaves 10..25 (1k..64M cycles) are resolved;
+// bucket 0 is cost 0 only (dead tiles), so the live-first prefix survives.
+// (Measured against whole octaves: 8-rank C2 share 1.035 -> 0.957 ms, C2
+// +1.3 %; eighth-octave buckets measured the same as quarter-octave ones.)
+__device__ __forceinline__ uint32_t tile_bucket(const uint32_t *cost, uint32_t i, uint32_t n) {
+    if (i >= n) return kSortBuckets;  // past the end
+    const uint32_t c = cost[i];
+    if (c == 0u) return 0u;
+    const int l = 31 - __builtin_clz(c);
+    const int q = 4 * l + (l >= 2 ? (int)((c >> (l - 2)) & 3u) : 0) - 40;
+    return (uint32_t)(q < 1 ? 1 : q > (int)kSortBuckets - 1 ? (int)kSortBuckets - 1 : q);
+}
+
+// lane k < kSortBuckets of the result: run[k] + (this wave's count of bucket k);
+// *rank: run[b] + this lane's position among the wave's lanes with bucket b
+__device__ __forceinline__ uint32_t wave_walk(uint32_t b, uint32_t run, uint32_t lane, uint32_t *rank) {
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t pend = b;
+    for (uint64_t live = __ballot(pend < kSortBuckets); live; live = __ballot(pend < kSortBuckets)) {
+        const uint32_t b0 = __builtin_amdgcn_readlane(pend, (int)__builtin_ctzll(live));
+        const uint64_t m = __ballot(pend == b0);
+        if (pend == b0) {
+            *rank = __builtin_amdgcn_readlane(run, (int)b0) + (uint32_t)__popcll(m & lt);
+            pend = kSortBuckets;
+        }
+        if (lane == b0) run += (uint32_t)__popcll(m);
+    }
+    return run;
+}
+
+__global__ __launch_bounds__(kSortBlock) void tile_count_kernel(const uint32_t *cost, uint32_t n, uint32_t *bcount) {
+    __shared__ uint32_t wc[kSortWaves][kSortBuckets];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t rank;
+    const uint32_t c = wave_walk(tile_bucket(cost, blockIdx.x * kSortBlock + threadIdx.x, n), 0u, lane, &rank);
+    if (lane < kSortBuckets) wc[wave][lane] = c;
+    __syncthreads();
+    if (threadIdx.x < kSortBuckets) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < kSortWaves; ++w) t += wc[w][threadIdx.x];
+        bcount[kSortBuckets * blockIdx.x + threadIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(1024) void tile_scan_kernel(uint32_t *bcount, uint32_t n_blk) {
+    __shared__ uint32_t part[1024];
+    __shared__ uint32_t stage[kScanLds];
+    const uint32_t len = kSortBuckets * n_blk, t = threadIdx.x, per = (len + 1023u) / 1024u;
+    const bool in_lds = len <= kScanLds;
+    if (in_lds)
+        for (uint32_t j = t; j < len; j += 1024u) stage[j] = bcount[j];
+    __syncthreads();
+    uint32_t *const src = in_lds ? stage : bcount;
+    // scan position p -> (bucket kSortBuckets-1 - p / n_blk, block p % n_blk)
+    auto at = [&](uint32_t p) -> uint32_t & { return src[kSortBuckets * (p % n_blk) + (kSortBuckets - 1u - p / n_blk)]; };
+    const uint32_t p0 = min(len, t * per), p1 = min(len, p0 + per);
+    uint32_t sum = 0;
+    for (uint32_t p = p0; p < p1; ++p) sum += at(p);
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {  // inclusive Hillis-Steele scan of the partials
+        const uint32_t x = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += x;
+        __syncthreads();
+    }
+    uint32_t off = part[t] - sum;
+    for (uint32_t p = p0; p < p1; ++p) {
+        const uint32_t c = at(p);
+        at(p) = off;
+        off += c;
+    }
+    __syncthreads();
+    if (in_lds)
+        for (uint32_t j = t; j < len; j += 1024u) bcount[j] = stage[j];
+}
+
+__global__ __launch_bounds__(kSortBlock) void tile_rank_kernel(uint32_t *cost, uint32_t n, const uint32_t *bbase,
+                                                               uint32_t *order) {
+    __shared__ uint32_t wc[kSortWaves][kSortBuckets];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kSortBlock + threadIdx.x, b = tile_bucket(cost, i, n);
+    uint32_t rank = 0;
+    const uint32_t c = wave_walk(b, 0u, lane, &rank);
+    if (lane < kSortBuckets) wc[wave][lane] = c;
+    __syncthreads();
+    if (threadIdx.x < kSortBuckets) {  // the block's base -> each wave's base, in wave order
+        uint32_t off = bbase[kSortBuckets * blockIdx.x + threadIdx.x];
+        for (uint32_t w = 0; w < kSortWaves; ++w) {
+            const uint32_t x = wc[w][threadIdx.x];
+            wc[w][threadIdx.x] = off;
+            off += x;
+        }
+    }
+    __syncthreads();
+    (void)wave_walk(b, lane < kSortBuckets ? wc[wave][lane] : 0u, lane, &rank);
+    if (b < kSortBuckets) {
+        order[rank] = i;
+        cost[i] = 0;  // measured afresh by the next launch
+    }
+}
+
+// ---- XCD grouping of the wave order (one-wave kernels).  Workgroups are dealt
+// round-robin to the 8 XCDs (block b and b + 8 share one; MI355X_MICROARCH.md,
+// "Workgroup dispatch"), so the four waves of a block tile, which store
+// neighbouring pixels of the same 128-B lines, land on up to four XCDs whose
+// L2s each write their part of every line back (the excess HBM writes of §4).
+// Grouping keeps the per-wave heaviest-first order but moves every unit of block
+// tile t into one XCD group x = grp[t] (below): the live prefix [0, L) of the sorted order is
+// partitioned stably by x (each group stays heaviest first), and group x's r-th
+// unit goes to position 8r + x while r < m (the smallest group's size), so block
+// 8r + x runs on the group's XCD; the r >= m leftovers (the lightest units of the
+// larger groups) follow at 8m + ..., group by group.  A permutation of [0, L):
+// no unit is lost or repeated; [L, n) (dead tiles' units) is copied as is.
+constexpr uint32_t kXgBlock = 1024, kXgWaves = kXgBlock / 64;
+
+// The group of a block tile is its rank, among the live tiles, in the order of
+// their heaviest wave (the tile's first unit in the sorted order), modulo 8: the
+// groups then take every eighth tile of a cost-sorted list, so the eight XCDs get
+// equal work (a group by tile & 7 measured C2 -1.2 %: its columns' costs differ).
+// xg_first_kernel: first[t] = the smallest sorted position of tile t's units;
+// xg_flag_count / xg_scan / xg_tile_rank: grp[t] = (rank of tile t among the live
+// tiles, by first[t]) & 7 (first and grp: two n_tiles-word arrays in aux).
+__device__ __forceinline__ uint32_t xg_group(const uint32_t *in, uint32_t i, uint32_t live_units,
+                                             const uint32_t *grp) {
+    return i < live_units ? grp[in[i] >> 2] : 8u;
+}
+
+__global__ __launch_bounds__(kXgBlock) void xg_first_kernel(const uint32_t *in, uint32_t n,
+                                                            const unsigned long long *live_tiles, uint32_t *first) {
+    const uint32_t i = blockIdx.x * kXgBlock + threadIdx.x;
+    const uint32_t L = (uint32_t)min((unsigned long long)n, 4ull * *live_tiles);
+    if (i < L) atomicMin(first + (in[i] >> 2), i);
+}
+
+// per block: the number of positions that are their tile's first (bc[blk])
+__global__ __launch_bounds__(kXgBlock) void xg_flag_count_kernel(const uint32_t *in, uint32_t n,
+                                                                 const unsigned long long *live_tiles,
+                                                                 const uint32_t *first, uint32_t *bc) {
+    __shared__ uint32_t wc[kXgWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, i = blockIdx.x * kXgBlock + threadIdx.x;
+    const uint32_t L = (uint32_t)min((unsigned long long)n, 4ull * *live_tiles);
+    const bool f = i < L && first[in[i] >> 2] == i;
+    const uint64_t m = __ballot(f);
+    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < kXgWaves; ++w) t += wc[w];
+        bc[blockIdx.x] = t;
+    }
+}
+
+// one wave: exclusive scan of bc[0, n_blk) in place
+__global__ __launch_bounds__(64) void xg_scan1_kernel(uint32_t *bc, uint32_t n_blk) {
+    if (threadIdx.x != 0) return;
+    uint32_t run = 0;
+    for (uint32_t b = 0; b < n_blk; ++b) {
+        const uint32_t c = bc[b];
+        bc[b] = run;
+        run += c;
+    }
+}
+
+__global__ __launch_bounds__(kXgBlock) void xg_tile_rank_kernel(const uint32_t *in, uint32_t n,
+                                                                const unsigned long long *live_tiles,
+                                                                const uint32_t *first, const uint32_t *bc,
+                                                                uint32_t *grp) {
+    __shared__ uint32_t wc[kXgWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, i = blockIdx.x * kXgBlock + threadIdx.x;
+    const uint32_t L = (uint32_t)min((unsigned long long)n, 4ull * *live_tiles);
+    const bool f = i < L && first[in[i] >> 2] == i;
+    const uint64_t m = __ballot(f);
+    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!f) return;
+    uint32_t rank = bc[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; ++w) rank += wc[w];
+    grp[in[i] >> 2] = rank & 7u;
+}
+
+__global__ __launch_bounds__(kXgBlock) void xg_count_kernel(const uint32_t *in, uint32_t n,
+                                                            const unsigned long long *live_tiles, const uint32_t *grp,
+                                                            uint32_t *bc) {
+    __shared__ uint32_t wc[kXgWaves][8];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, i = blockIdx.x * kXgBlock + threadIdx.x;
+    const uint32_t L = (uint32_t)min((unsigned long long)n, 4ull * *live_tiles);
+    const uint32_t x = xg_group(in, i, L, grp);
+    for (uint32_t v = 0; v < 8u; ++v) {
+        const uint64_t m = __ballot(x == v);
+        if (lane == v) wc[wave][v] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < 8u) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < kXgWaves; ++w) t += wc[w][threadIdx.x];
+        bc[8u * blockIdx.x + threadIdx.x] = t;
+    }
+}
+
+// one wave: per-group exclusive scan over the blocks (in place), then the group
+// sizes c_x, m = min c_x and the leftover bases at bc[8 n_blk ..]
+__global__ __launch_bounds__(64) void xg_scan_kernel(uint32_t *bc, uint32_t n_blk) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t run = 0;
+    if (lane < 8u)
+        for (uint32_t b = 0; b < n_blk; ++b) {
+            const uint32_t c = bc[8u * b + lane];
+            bc[8u * b + lane] = run;
+            run += c;
+        }
+    uint32_t m = lane < 8u ? run : 0xFFFFFFFFu;
+    for (int off = 1; off < 8; off <<= 1) m = min(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    m = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+    // base_x = sum over y < x of (c_y - m)
+    uint32_t extra = lane < 8u ? run - m : 0u, base = 0;
+    for (uint32_t y = 0; y < 8u; ++y) {
+        const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)extra, (int)y);
+        if (y < lane) base += e;
+    }
+    if (lane == 0) bc[8u * n_blk] = m;
+    if (lane < 8u) bc[8u * n_blk + 1u + lane] = base;
+}
+
+__global__ __launch_bounds__(kXgBlock) void xg_place_kernel(const uint32_t *in, uint32_t *out, uint32_t n,
+                                                            const unsigned long long *live_tiles, const uint32_t *grp,
+                                                            const uint32_t *bc, uint32_t n_blk) {
+    __shared__ uint32_t wc[kXgWaves][8];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, i = blockIdx.x * kXgBlock + threadIdx.x;
+    const uint32_t L = (uint32_t)min((unsigned long long)n, 4ull * *live_tiles);
+    const uint32_t x = xg_group(in, i, L, grp);
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t rank = 0;
+    for (uint32_t v = 0; v < 8u; ++v) {
+        const uint64_t m = __ballot(x == v);
+        if (x == v) rank = (uint32_t)__popcll(m & lt);
+        if (lane == v) wc[wave][v] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (i >= n) return;
+    if (x >= 8u) {  // a dead tile's unit (or past the live prefix): unchanged
+        out[i] = in[i];
+        return;
+    }
+    for (uint32_t w = 0; w < wave; ++w) rank += wc[w][x];
+    const uint32_t r = bc[8u * blockIdx.x + x] + rank;
+    const uint32_t m = bc[8u * n_blk];
+    const uint32_t pos = r < m ? 8u * r + x : 8u * m + bc[8u * n_blk + 1u + x] + (r - m);
+    out[pos] = in[i];
+}
+}  // namespace rtk
+
+extern "C" size_t rtk_tile_sort_scratch(uint32_t n) {
+    return rtk::kSortBuckets * 4u * (size_t)((n + rtk::kSortBlock - 1u) / rtk::kSortBlock);
+}
+
+extern "C" int rtk_launch_tile_sort(uint32_t *cost, uint32_t *order, uint32_t *scratch, uint32_t n, hipStream_t stream) {
+    const uint32_t n_blk = (n + rtk::kSortBlock - 1u) / rtk::kSortBlock;
+    if (n_blk == 0) return 0;
+    const dim3 grid(n_blk), block(rtk::kSortBlock);
+    hipLaunchKernelGGL(rtk::tile_count_kernel, grid, block, 0, stream, (const uint32_t *)cost, n, scratch);
+    hipLaunchKernelGGL(rtk::tile_scan_kernel, dim3(1), dim3(1024), 0, stream, scratch, n_blk);
+    hipLaunchKernelGGL(rtk::tile_rank_kernel, grid, block, 0, stream, cost, n, (const uint32_t *)scratch, order);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int rtk_launch_xcd_group(const uint32_t *order_in, uint32_t *order_out, uint32_t n_units,
+                                    const unsigned long long *live_tiles, uint32_t *scratch, uint32_t *aux,
+                                    hipStream_t stream) {
+    const uint32_t n_blk = (n_units + rtk::kXgBlock - 1u) / rtk::kXgBlock;
+    if (n_blk == 0) return 0;
+    const uint32_t n_tiles = (n_units + 3u) / 4u;
+    uint32_t *first = aux, *grp = aux + n_tiles;
+    const dim3 grid(n_blk), block(rtk::kXgBlock);
+    if (hipMemsetAsync(first, 0xFF, (size_t)n_tiles * 4u, stream) != hipSuccess) return -5;
+    hipLaunchKernelGGL(rtk::xg_first_kernel, grid, block, 0, stream, order_in, n_units, live_tiles, first);
+    hipLaunchKernelGGL(rtk::xg_flag_count_kernel, grid, block, 0, stream, order_in, n_units, live_tiles,
+                       (const uint32_t *)first, scratch);
+    hipLaunchKernelGGL(rtk::xg_scan1_kernel, dim3(1), dim3(64), 0, stream, scratch, n_blk);
+    hipLaunchKernelGGL(rtk::xg_tile_rank_kernel, grid, block, 0, stream, order_in, n_units, live_tiles,
+                       (const uint32_t *)first, (const uint32_t *)scratch, grp);
+    hipLaunchKernelGGL(rtk::xg_count_kernel, grid, block, 0, stream, order_in, n_units, live_tiles,
+                       (const uint32_t *)grp, scratch);
+    hipLaunchKernelGGL(rtk::xg_scan_kernel, dim3(1), dim3(64), 0, stream, scratch, n_blk);
+    hipLaunchKernelGGL(rtk::xg_place_kernel, grid, block, 0, stream, order_in, order_out, n_units, live_tiles,
+                       (const uint32_t *)grp, (const uint32_t *)scratch, n_blk);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" uint32_t rtk_tiles_x(uint32_t width, int lanes_per_pixel) {
+    return rtk_tile_count(width, 1u, lanes_per_pixel);
+}
+
+extern "C" uint32_t rtk_tile_count(uint32_t width, uint32_t local_rows, int lanes_per_pixel) {
+    uint32_t bw = 16u, bh = 16u;  // 2*TW x 2*TH of the launch's shape
+    switch (lanes_per_pixel) {
+        case 32: bw = 2u * rtk::Shape<32>::TW; bh = 2u * rtk::Shape<32>::TH; break;
+        case 16: bw = 2u * rtk::Shape<16>::TW; bh = 2u * rtk::Shape<16>::TH; break;
+        case 8: bw = 2u * rtk::Shape<8>::TW; bh = 2u * rtk::Shape<8>::TH; break;
+        case 4: bw = 2u * rtk::Shape<4>::TW; bh = 2u * rtk::Shape<4>::TH; break;
+        case 2: bw = 2u * rtk::Shape<2>::TW; bh = 2u * rtk::Shape<2>::TH; break;
+        case 0: bw = 2u * rtk::Shape<0>::TW; bh = 2u * rtk::Shape<0>::TH; break;
+        default: bw = 2u * rtk::Shape<1>::TW; bh = 2u * rtk::Shape<1>::TH; break;
+    }
+    return ((width + bw - 1u) / bw) * ((local_rows + bh - 1u) / bh);
+}
+
+namespace rtk {
+// The primary rounds' group rows for this camera (TraceArgs.prim): one sphere
+// slot per thread, c = RN(centre - CameraPosition) as main.cpp:401 rounds it
+// (one f32 subtraction: no contraction, IEEE denormals), and r*r copied.
+__global__ __launch_bounds__(256) void prim_kernel(TraceArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;  // sphere slot 4 g + l
+    if (i >= 4u * a.n_groups) return;
+    const uint32_t g = i >> 2, l = i & 3u;
+    const float *src = reinterpret_cast<const float *>(a.groups + (size_t)kGroupF4 * g);
+    float *dst = reinterpret_cast<float *>(a.prim + (size_t)kPrimF4 * g);
+    dst[0u + l] = src[4u * kRowX + l] - a.cam_pos[0];
+    dst[4u + l] = src[4u * kRowY + l] - a.cam_pos[1];
+    dst[8u + l] = src[4u * kRowZ + l] - a.cam_pos[2];
+    dst[12u + l] = src[4u * kRowR2 + l];
+}
+}  // namespace rtk
+
+template <int P>
+static void launch_cull_p(const TraceArgs *a, uint32_t *live, uint32_t *cost, unsigned long long *counters,
+                          int empty_capable, hipStream_t stream) {
+    const uint32_t n = rtk_tile_count(a->width, a->local_rows, P);
+    if (a->n_groups)
+        hipLaunchKernelGGL(rtk::prim_kernel, dim3((4u * a->n_groups + 255u) / 256u), dim3(256), 0, stream, *a);
+    (void)hipMemsetAsync(counters, 0, 2u * rtk::kCullStripes * sizeof(unsigned long long), stream);
+    hipLaunchKernelGGL(rtk::cull_kernel<P>, dim3(n), dim3(256), 0, stream, *a, live, cost, counters,
+                       (uint32_t)(empty_capable != 0));
+    hipLaunchKernelGGL(rtk::cull_total_kernel, dim3(1), dim3(64), 0, stream, counters);
+}
+
+extern "C" int rtk_launch_cull(const TraceArgs *a, int lanes_per_pixel, uint32_t *live, uint32_t *cost,
+                               unsigned long long *counters, int empty_capable, hipStream_t stream) {
+    if (!a->masks || !a->prim) return -1;
+    RTK_BY_P(launch_cull_p, a, live, cost, counters, empty_capable, stream)
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+template <int P>
+static void launch_empty_p(const TraceArgs *a, const uint32_t *live, const unsigned long long *dead_pixels,
+                           hipStream_t stream) {
+    hipLaunchKernelGGL(rtk::empty_kernel<P>, dim3((a->width + 255u) / 256u, a->local_rows), dim3(256), 0, stream, *a,
+                       live, dead_pixels);
+}
+
+extern "C" int rtk_launch_empty(const TraceArgs *a, int lanes_per_pixel, const uint32_t *live,
+                                const unsigned long long *dead_pixels, hipStream_t stream) {
+    RTK_BY_P(launch_empty_p, a, live, dead_pixels, stream)
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+template <int P>
+static void launch_pixel_sort_p(const TraceArgs *a, uint8_t *perm, hipStream_t stream) {
+    const uint32_t n = rtk_tile_count(a->width, a->local_rows, P);
+    hipLaunchKernelGGL(rtk::pixel_sort_kernel<P>, dim3(n), dim3(64), 0, stream, *a, perm);
+}
+
+extern "C" int rtk_launch_pixel_sort(const TraceArgs *a, int lanes_per_pixel, uint8_t *perm, hipStream_t stream) {
+    switch (a->pix_cost ? lanes_per_pixel : 0) {  // (a block tile of 64 pixels at most: P >= 4)
+        case 32: launch_pixel_sort_p<32>(a, perm, stream); break;
+        case 16: launch_pixel_sort_p<16>(a, perm, stream); break;
+        case 8: launch_pixel_sort_p<8>(a, perm, stream); break;
+        case 4: launch_pixel_sort_p<4>(a, perm, stream); break;
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+namespace rtk {
+// Re-encode a resident running mean (v4 f32) as RGBA8: the store of
+// main.cpp:490 on its own (rt_encode_rgba8).
+__global__ __launch_bounds__(256) void encode_kernel(const float4 *accum, uint32_t *out, uint64_t n, uint32_t pw) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const float4 v = accum[i];
+        out[i] = rgba8(v.x, v.y, v.z, pw != 0u);
+    }
+}
+}  // namespace rtk
+
+extern "C" int rtk_launch_encode(const void *accum, void *out, uint64_t n, uint32_t pow_mode, hipStream_t stream) {
+    if (n == 0) return 0;
+    const uint64_t blocks = (n + 255u) / 256u;
+    const uint32_t grid = (uint32_t)(blocks < 8192u ? blocks : 8192u);
+    hipLaunchKernelGGL(rtk::encode_kernel, dim3(grid), dim3(256), 0, stream, (const float4 *)accum, (uint32_t *)out, n,
+                       pow_mode);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+__global__ void sum_u64_kernel(const uint64_t *slots, uint32_t n, uint64_t *dst) {
+    if (threadIdx.x != 0) return;
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < n; ++i) s += slots[i];
+    dst[0] += s;
+}
+
+extern "C" int rtk_launch_sum_u64(const uint64_t *slots, uint32_t n, uint64_t *dst, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_u64_kernel, dim3(1), dim3(64), 0, stream, slots, n, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int rtk_launch_assemble(const void *src, uint64_t rank_stride, void *dst, uint32_t width, uint32_t height,
+                                   uint32_t elem, uint32_t band_rows, uint32_t band_count, hipStream_t stream) {
+    const dim3 block(256);
+    const dim3 grid(4, height);
+    hipLaunchKernelGGL(rtk::assemble_kernel, grid, block, 0, stream, (const uint8_t *)src, rank_stride, (uint8_t *)dst,
+                       width, height, elem, band_rows, band_count);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}

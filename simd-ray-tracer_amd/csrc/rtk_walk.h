@@ -1,0 +1,751 @@
+// rtk_walk.h — the sphere walks of the trace kernel: group loaders, the exact
+// packed pair test and candidate logic, the FMA prefilter and its exact
+// recheck, the clustered prefilter walk, and the primary rounds' pair test.
+#pragma once
+#include "rtk_math.h"
+
+namespace rtk {
+
+struct Group {
+    float x[4], y[4], z[4], r2[4];
+    float r2p[4];  // prefilter threshold r^2 + E (see pair_prefilter)
+};
+
+__device__ __forceinline__ void group_rows(Group &G, float4 x, float4 y, float4 z, float4 r2p, float4 r2) {
+    G.x[0] = x.x; G.x[1] = x.y; G.x[2] = x.z; G.x[3] = x.w;
+    G.y[0] = y.x; G.y[1] = y.y; G.y[2] = y.z; G.y[3] = y.w;
+    G.z[0] = z.x; G.z[1] = z.y; G.z[2] = z.z; G.z[3] = z.w;
+    G.r2p[0] = r2p.x; G.r2p[1] = r2p.y; G.r2p[2] = r2p.z; G.r2p[3] = r2p.w;
+    G.r2[0] = r2.x; G.r2[1] = r2.y; G.r2[2] = r2.z; G.r2[3] = r2.w;
+}
+
+// Group rows from the constant address space: read-only for the kernel's
+// lifetime, so a wave-uniform address always becomes s_loads into SGPRs
+// (immediate offsets from one base: rows 0-3 one dwordx16, row 4 a dwordx4).
+// Rows 0-3 hold the centres and r*r, all an exact test reads; row 4 the prefilter thresholds.
+typedef float v4f_t __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) v4f_t cv4f_t;
+__device__ __forceinline__ float4 f4(v4f_t v) { return make_float4(v.x, v.y, v.z, v.w); }
+// Rows 0-3 of a group record or of a cluster-table entry: one contiguous 64 B
+// block at a 16 B aligned address, read as ONE s_load_dwordx16 (row by row the
+// backend issued a dwordx8 and two dwordx4 for it: three scalar-memory
+// instructions and their address setup per entry of the walk).
+typedef float v16f_t __attribute__((ext_vector_type(16)));
+typedef v16f_t v16f_a16_t __attribute__((aligned(16)));
+typedef const __attribute__((address_space(4))) v16f_a16_t cv16f_t;
+struct Rows4 {
+    v4f_t r0, r1, r2, r3;
+};
+__device__ __forceinline__ Rows4 load_rows4(cv4f_t *e) {
+    const v16f_t v = *(cv16f_t *)e;
+    return {__builtin_shufflevector(v, v, 0, 1, 2, 3), __builtin_shufflevector(v, v, 4, 5, 6, 7),
+            __builtin_shufflevector(v, v, 8, 9, 10, 11), __builtin_shufflevector(v, v, 12, 13, 14, 15)};
+}
+static_assert(kRowX == 0 && kRowY == 1 && kRowZ == 2 && kRowR2 == 3 && kRowR2P == 4, "group rows 0-3: centres and r*r");
+__device__ __forceinline__ Group load_group_at(cv4f_t *cg) {
+    Group G;
+    const Rows4 r = load_rows4(cg);
+    group_rows(G, f4(r.r0), f4(r.r1), f4(r.r2), f4(cg[kRowR2P]), f4(r.r3));
+    return G;
+}
+
+template <int SRC>
+__device__ __forceinline__ Group load_group(const TraceArgs &a, const float4 *lds_groups, uint32_t g) {
+    if (SRC == kSrcSmem) return load_group_at((cv4f_t *)a.groups + kGroupF4 * g);
+    Group G;
+    const float4 *r = lds_groups + kGroupF4 * g;
+    group_rows(G, r[kRowX], r[kRowY], r[kRowZ], r[kRowR2P], r[kRowR2]);
+    return G;
+}
+
+// The shared part of one sphere test: T, |C - D*T|^2 (main.cpp:401-407).
+__device__ __forceinline__ void sphere_core(const Sample &p, float sx, float sy, float sz, float &T, float &dist) {
+    const float cx = sx - p.rx.x, cy = sy - p.ry.x, cz = sz - p.rz.x;
+    T = dot3(cx, cy, cz, p.rx.y, p.ry.y, p.rz.y);
+    const float qx = cx - p.rx.y * T, qy = cy - p.ry.y * T, qz = cz - p.rz.y * T;
+    dist = dot3(qx, qy, qz, qx, qy, qz);
+}
+
+// Per-lane hit state.  SIMD rules: the reference's four lane minima
+// (MinT / MaterialIndex / InsideSphere, main.cpp:394-396), one per residue
+// class s & 3.  Scalar rules use slot 0 only (main.cpp:541-545).
+struct Hit {
+    float t0, t1, t2, t3;
+    uint32_t g0, g1, g2, g3;
+    uint32_t ins;
+};
+
+__device__ __forceinline__ void hit_reset(Hit &h) {
+    h.t0 = h.t1 = h.t2 = h.t3 = kFMax;
+    h.g0 = h.g1 = h.g2 = h.g3 = 0;
+    h.ins = 0;
+}
+
+// Exact intersection of one candidate sphere (main.cpp:413-429 / 561-578),
+// given its T and |C - D*T|^2 from the packed distance test.
+// fast: the host proved every hittable r^2 is 0 or in [2^-36, 2^60], so
+// r^2 - dist (positive, hence >= ulp(r^2)/2, or exactly 0) is inside sqrt_rn's
+// verified range.
+template <bool SIMD, int L>
+__device__ __forceinline__ void candidate(Hit &h, uint32_t g, float T, float dist, float r2, bool fast) {
+    const float X = fast ? sqrt_rn(r2 - dist) : __builtin_sqrtf(r2 - dist);
+    float it = T - X;
+    const bool in = it < kEps;
+    if (in) it = T + X;
+    if (SIMD) {
+        float &tl = L == 0 ? h.t0 : L == 1 ? h.t1 : L == 2 ? h.t2 : h.t3;
+        uint32_t &gl = L == 0 ? h.g0 : L == 1 ? h.g1 : L == 2 ? h.g2 : h.g3;
+        if (it < tl && it > kEps) {  // strict: the earliest group keeps a tie
+            tl = it;
+            gl = g;
+            h.ins |= (in ? 1u : 0u) << L;  // sticky OR (main.cpp:425)
+        }
+    } else {
+        if (!(it > h.t0) && !(it < kEps)) {  // the later sphere wins a tie
+            h.t0 = it;
+            h.g0 = 4u * g + (uint32_t)L;
+            h.ins = in ? 1u : 0u;
+        }
+    }
+}
+
+
+// T and |C - D*T|^2 for two spheres of a group at once: every f32 op of
+// main.cpp:401-407 becomes one packed v_pk_{add,mul}_f32 over the pair (same
+// IEEE rounding per element; a packed op issues at the cost of a scalar one
+// on gfx950, so this halves the sphere loop's VALU instructions).
+// The ray as three {origin, direction} register pairs: a packed op can then
+// broadcast either half to both lanes with op_sel / op_sel_hi, so the pair
+// test needs no duplicated (splat) copies of the ray.
+struct RayPk {
+    f2 x, y, z;  // {o, d} per axis
+};
+
+__device__ __forceinline__ f2 pair_dist(const RayPk &r, f2 sx, f2 sy, f2 sz, f2 &T) {
+    f2 cx, cy, cz, t, d;
+    // c = s - o ; T = (cx*dx + cy*dy) + cz*dz ; q = c - d*T (in c) ;
+    // dist = (qx*qx + qy*qy) + qz*qz  -- op for op the reference's f32 sequence
+    asm("v_pk_add_f32 %[cx], %[sx], %[rx] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[cy], %[sy], %[ry] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[cz], %[sz], %[rz] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[t], %[cx], %[rx] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_mul_f32 %[d], %[cy], %[ry] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[T], %[t], %[d]\n\t"
+        "v_pk_mul_f32 %[t], %[cz], %[rz] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[T], %[T], %[t]\n\t"
+        "v_pk_mul_f32 %[t], %[rx], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[cx], %[cx], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[t], %[ry], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[cy], %[cy], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[t], %[rz], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[cz], %[cz], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[d], %[cx], %[cx]\n\t"
+        "v_pk_mul_f32 %[t], %[cy], %[cy]\n\t"
+        "v_pk_add_f32 %[d], %[d], %[t]\n\t"
+        "v_pk_mul_f32 %[t], %[cz], %[cz]\n\t"
+        "v_pk_add_f32 %[d], %[d], %[t]"
+        : [cx] "=&v"(cx), [cy] "=&v"(cy), [cz] "=&v"(cz), [t] "=&v"(t), [T] "=&v"(T), [d] "=&v"(d)
+        : [sx] "s"(sx), [sy] "s"(sy), [sz] "s"(sz), [rx] "v"(r.x), [ry] "v"(r.y), [rz] "v"(r.z));
+    return d;
+}
+
+// Secondary-ray prefilter: an FMA estimate of |C - D*T|^2 for two spheres
+// in 10 packed ops instead of the exact test's 19:
+//   C = S - O ;  cc = |C|^2 ;  T = C.D ;  e = cc - T*T      (fused)
+// For |D|^2 within K = 2^-16 of 1 and every origin on a sphere of the scene
+// (true for all secondary rays: NextRayOrigin is a hit point), |e - dist|
+// where dist is the reference's exactly-rounded value (main.cpp:401-407) is
+// below E_j = M_j (32u + 1.01K), u = 2^-24, M_j a bound on |C|^2 for
+// sphere j over every such origin (derivation: DESIGN.md).  The host stores
+// r2p_j >= r^2_j + E_j (rounded up), so e >= r2p proves dist > r^2 -- the
+// sphere is missed under both rule sets -- and only groups where some lane
+// fails that proof run the exact test.  A wave with any lane outside the
+// |D|^2 bound runs the exact loop instead.
+__device__ __forceinline__ f2 pair_prefilter(const RayPk &r, f2 sx, f2 sy, f2 sz, f2 &T, f2 &cc) {
+    f2 cx, cy, cz, e;
+    asm("v_pk_add_f32 %[cx], %[sx], %[rx] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[cy], %[sy], %[ry] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[cz], %[sz], %[rz] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[cc], %[cz], %[cz]\n\t"
+        "v_pk_fma_f32 %[cc], %[cy], %[cy], %[cc]\n\t"
+        "v_pk_fma_f32 %[cc], %[cx], %[cx], %[cc]\n\t"
+        "v_pk_mul_f32 %[T], %[cx], %[rx] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_fma_f32 %[T], %[cy], %[ry], %[T] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[T], %[cz], %[rz], %[T] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[e], %[T], %[T], %[cc] neg_lo:[1,0,0] neg_hi:[1,0,0]"
+        : [cx] "=&v"(cx), [cy] "=&v"(cy), [cz] "=&v"(cz), [cc] "=&v"(cc), [T] "=&v"(T), [e] "=&v"(e)
+        : [sx] "s"(sx), [sy] "s"(sy), [sz] "s"(sz), [rx] "v"(r.x), [ry] "v"(r.y), [rz] "v"(r.z));
+    return e;
+}
+
+// The exact recheck of one group's flagged sphere pairs (f01, f23): only such
+// a pair reruns the exact packed test (same ops as test_group) and the exact
+// candidate logic decides, so results are identical.
+// The group's r^2 row comes with its centres (rows 0-3 of the record, one
+// scalar load: load_group_exact_at / load_group_at).
+template <bool SIMD>
+__device__ __forceinline__ void recheck_pairs(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
+                                              bool f01, bool f23) {
+    const float4 r2 = make_float4(G.r2[0], G.r2[1], G.r2[2], G.r2[3]);
+    if (f01) {
+        f2 T01;
+        const f2 d01 = pair_dist(p, f2{G.x[0], G.x[1]}, f2{G.y[0], G.y[1]}, f2{G.z[0], G.z[1]}, T01);
+        const uint32_t s0 = 4u * g;
+        const bool h0 = SIMD ? d01.x < r2.x : s0 + 0u < a.n_spheres && !(d01.x > r2.x);
+        const bool h1 = SIMD ? d01.y < r2.y : s0 + 1u < a.n_spheres && !(d01.y > r2.y);
+        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, r2.x, fast);
+        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, r2.y, fast);
+    }
+    if (f23) {
+        f2 T23;
+        const f2 d23 = pair_dist(p, f2{G.x[2], G.x[3]}, f2{G.y[2], G.y[3]}, f2{G.z[2], G.z[3]}, T23);
+        const uint32_t s0 = 4u * g;
+        const bool h2 = SIMD ? d23.x < r2.z : s0 + 2u < a.n_spheres && !(d23.x > r2.z);
+        const bool h3 = SIMD ? d23.y < r2.w : s0 + 3u < a.n_spheres && !(d23.y > r2.w);
+        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, r2.z, fast);
+        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, r2.w, fast);
+    }
+}
+
+// Per-lane ("relative") prefilter threshold: t = RN(cc * 2^-15 + r^2) with
+// cc = the lane's computed |C|^2, where the threshold row (kRowR2P) holds r^2 (-inf: never hit).
+// The error bound of e (and of the reference-rounded dist) scales with the
+// lane's own |C|^2 instead of the scene-wide M_j, so the test still proves
+// misses in scenes whose M_j bound is useless (RTWeekend's ground sphere
+// makes M ~ 1.6e4 against r^2 ~ 1.6e-4).  Proof: with
+// |C|^2 <= cc (1 + 5u) and E = 23.5u + K(1+K) the combined error of e and of
+// the reference's dist relative to |C|^2, e >= t gives dist > r^2 whenever
+// cc >= r^2 / 232 (then cc (2^-15 (1-u) - (1+5u) E) >= u r^2 covers t's own
+// rounding); and when cc < r^2 / 232, e <= cc < t, so nothing is skipped.
+constexpr float kPfRel = 0x1p-15f;
+
+// Prefilter flags of group G's two sphere pairs for this lane's ray.
+template <bool REL>
+__device__ __forceinline__ void prefilter_group(const Group &G, const RayPk &p, bool &f01, bool &f23) {
+    f2 T01, T23, c01, c23;
+    const f2 e01 = pair_prefilter(p, f2{G.x[0], G.x[1]}, f2{G.y[0], G.y[1]}, f2{G.z[0], G.z[1]}, T01, c01);
+    const f2 e23 = pair_prefilter(p, f2{G.x[2], G.x[3]}, f2{G.y[2], G.y[3]}, f2{G.z[2], G.z[3]}, T23, c23);
+    if (REL) {
+        f01 = !(e01.x >= __builtin_fmaf(c01.x, kPfRel, G.r2p[0])) | !(e01.y >= __builtin_fmaf(c01.y, kPfRel, G.r2p[1]));
+        f23 = !(e23.x >= __builtin_fmaf(c23.x, kPfRel, G.r2p[2])) | !(e23.y >= __builtin_fmaf(c23.y, kPfRel, G.r2p[3]));
+    } else {
+        f01 = !(e01.x >= G.r2p[0]) | !(e01.y >= G.r2p[1]);
+        f23 = !(e23.x >= G.r2p[2]) | !(e23.y >= G.r2p[3]);
+    }
+}
+
+// The prefiltered walks' counters of the diagnostic build (rtk_trace.h TraceStats; clustered_groups says
+// what each counts there)
+struct PfStats {
+    uint32_t groups, cl_tested, pairs, cl_top_entered, lane_pairs;
+};
+
+// Group g for a secondary ray through the prefilter: one wave branch per
+// group, and inside it one per flagged pair.  (Measured: +5.5 % on C2 over
+// one exact recheck of both pairs per flagged group.)
+template <bool SIMD, bool GS, bool REL>
+__device__ __forceinline__ void test_group_pf(const TraceArgs &a, const float4 *lds_groups, const Group &G, uint32_t g,
+                                              const RayPk &p, Hit &h, bool fast, PfStats *ps = nullptr) {
+    bool f01, f23;
+    prefilter_group<REL>(G, p, f01, f23);
+    if (ps) {
+        ps->groups += __ballot(f01 | f23) != 0;
+        ps->pairs += (__ballot(f01) != 0) + (__ballot(f23) != 0);
+        ps->lane_pairs += __builtin_popcountll(__ballot(f01)) + __builtin_popcountll(__ballot(f23));
+    }
+    if (f01 | f23) recheck_pairs<SIMD>(a, G, g, p, h, fast, f01, f23);
+}
+
+template <bool SIMD>
+__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
+                                           uint32_t *hit_groups);
+
+// Rows 0-3 only (one s_load_dwordx16): what the exact recheck of the cluster walk reads.
+__device__ __forceinline__ Group load_group_exact_at(cv4f_t *cg) {
+    Group G;
+    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const Rows4 r = load_rows4(cg);
+    group_rows(G, f4(r.r0), f4(r.r1), f4(r.r2), z4, f4(r.r3));
+    return G;
+}
+
+// The full sphere loop over all groups from SGPRs.  PF: secondary rays
+// through the prefilter; else the exact test.
+template <bool SIMD, bool PF, bool GS, bool REL = false>
+__device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray, Hit &h, bool fast,
+                                                uint32_t *hit_groups, PfStats *ps = nullptr) {
+    cv4f_t *gp = (cv4f_t *)a.groups;
+    // one group in SGPRs at a time: its s_load (scalar-cache hit) is covered
+    // by the other waves on the SIMD -- measured as fast as a ping-pong
+    // prefetch, at half the SGPRs (and two groups per trip under one branch
+    // measured 2 % slower)
+    for (uint32_t g = 0; g < a.n_groups; ++g, gp += kGroupF4) {
+        const Group G = load_group_at(gp);
+        if (PF) test_group_pf<SIMD, GS, REL>(a, lds_groups, G, g, ray, h, fast, ps);
+        else test_group<SIMD>(a, G, g, ray, h, fast, hit_groups);
+    }
+}
+
+// The clustered prefilter (secondary rays; rt_host.cpp cluster_table proves
+// it).  A wave tests the ray against about sqrt(n) cluster bounding volumes,
+// two per packed prefilter, and only the members of a cluster some lane may
+// reach run the per-sphere prefilter; a sphere pair some lane may hit sets
+// bit (slot >> 1) of the wave's pair mask (W u64 words, SGPRs only; W = 1
+// tables carry the bit itself, W = 2 tables the pair index).  The
+// exact recheck then walks the flagged groups in ascending order -- the
+// reference's order, so the per-class minima, tie rules and sticky inside flags
+// come out as in the full loop.  The recheck runs on every lane: a lane whose
+// own estimate cleared the pair has a proven miss there, which its exact test
+// reproduces, so no per-lane flags are needed.
+constexpr int kClWords = 4;  // pair-mask words (n_groups <= 128)
+// Per-lane thresholds (pf_relative, rt_host.cpp cluster_table "relative"):
+// cluster: e_c >= RN(cc kClRel + R_c); sphere: e >= RN(cc kPfRel + r^2) (kPfRel
+// below); behind: T < RN(b - cc kBehindRel).
+constexpr float kClRel = 9.2e-4f;               // >= (a + a^2 + E1)(1 + 6u), a = 8.917e-4
+constexpr float kBehindRel = 4.5f * 0x1p-24f;    // >= 4.3u (|Q|, |C_j| <= (1 + cc)/2)
+
+// ballot(a && b) as ballot(a) & ballot(b): the backend folds the ballot of a
+// single compare into the v_cmp's own lane mask, but materialises the ballot of
+// a conjunction through v_cndmask + v_cmp_ne (two VALU per ballot)
+__device__ __forceinline__ uint64_t ballot_and(bool a, bool b) {
+    return __builtin_amdgcn_ballot_w64(a) & __builtin_amdgcn_ballot_w64(b);
+}
+
+// One trip's round decision (trace_kernel), on the scalar unit in six instructions:
+//   pri    = want & ring                   the lanes that can start their pending sample
+//   do_sec = popcount(sec) >= (pri ? thr : 1)
+//          = sec != 0 && (pri == 0 || popcount(sec) >= thr) for thr >= 1 (rt_host.cpp sets no 0)
+//   round  = do_sec ? sec : pri            the lanes this round traces
+// The conjunction's own SCC (pri != 0) picks the count to compare against and the compare's SCC
+// picks the round's mask (as merge_word1 does); the compiler's lowering turned each compare into
+// a 64-bit lane mask (s_cselect_b64 -1/0) and combined and re-tested the masks -- about 20
+// scalar instructions for the same three values.  do_sec comes back as an integer so that its
+// later tests are scalar compares of it, not further lane masks.
+__device__ __forceinline__ void round_select(uint64_t want, uint64_t ring, uint64_t sec, uint32_t thr, uint64_t &pri,
+                                             uint32_t &do_sec, uint64_t &round) {
+    uint32_t need;
+    asm("s_and_b64 %[pri], %[want], %[ring]\n\t"
+        "s_cselect_b32 %[need], %[thr], 1\n\t"
+        "s_bcnt1_i32_b64 %[ds], %[sec]\n\t"
+        "s_cmp_ge_u32 %[ds], %[need]\n\t"
+        "s_cselect_b32 %[ds], 1, 0\n\t"
+        "s_cselect_b64 %[rnd], %[sec], %[pri]"
+        : [pri] "=&s"(pri), [need] "=&s"(need), [ds] "=&s"(do_sec), [rnd] "=&s"(round)
+        : [want] "s"(want), [ring] "s"(ring), [sec] "s"(sec), [thr] "s"(thr)
+        : "scc");
+}
+
+// (a | b) != 0 as an integer from the OR's own SCC: the test of it is then one scalar compare
+__device__ __forceinline__ uint32_t any_lane(uint64_t a, uint64_t b) {
+    uint64_t t;
+    uint32_t r;
+    asm("s_or_b64 %[t], %[a], %[b]\n\t"
+        "s_cselect_b32 %[r], 1, 0"
+        : [t] "=&s"(t), [r] "=&s"(r)
+        : [a] "s"(a), [b] "s"(b)
+        : "scc");
+    return r;
+}
+
+// Entry e of the cluster table at byte offset off (a 32-bit offset from the
+// table's base keeps the per-entry address arithmetic to one SALU add).
+__device__ __forceinline__ cv4f_t *cl_entry(cv4f_t *ct, uint32_t off) {
+    return (cv4f_t *)((const __attribute__((address_space(4))) char *)ct + off);
+}
+
+// The member pairs [first, first + count) of an entered cluster: a sphere pair
+// some lane may hit ORs its word-w bits into every word w of the wave's pair
+// mask (rt_kernel.h: the entry's row of word w holds the bit or 0).  The walk is
+// SALU-heavy (ballots, mask merges, loop control issue on the CU's one scalar
+// unit): C5's member loop at 48 SALU per entry ran 17 % slower than at 34.
+// wave[w] |= f ? bits[w] : 0 for every word under one compare of the ballot f:
+// s_cselect_b64 per word (the compiler's lowering selects 32-bit halves, two
+// per word) -- the merge runs on the CU's one scalar unit for every member.
+template <int W>
+__device__ __forceinline__ void merge_words(uint64_t (&wave)[kClWords], uint64_t f, const uint64_t (&bits)[W]) {
+    uint64_t t0, t1;
+    if constexpr (W == 2) {
+        asm("s_cmp_lg_u64 %[f], 0\n\t"
+            "s_cselect_b64 %[t0], %[b0], 0\n\t"
+            "s_cselect_b64 %[t1], %[b1], 0\n\t"
+            "s_or_b64 %[w0], %[w0], %[t0]\n\t"
+            "s_or_b64 %[w1], %[w1], %[t1]"
+            : [w0] "+s"(wave[0]), [w1] "+s"(wave[1]), [t0] "=&s"(t0), [t1] "=&s"(t1)
+            : [f] "s"(f), [b0] "s"(bits[0]), [b1] "s"(bits[1])
+            : "scc");
+    } else {
+        static_assert(W == 4, "pair-mask words");
+        uint64_t t2, t3;
+        asm("s_cmp_lg_u64 %[f], 0\n\t"
+            "s_cselect_b64 %[t0], %[b0], 0\n\t"
+            "s_cselect_b64 %[t1], %[b1], 0\n\t"
+            "s_cselect_b64 %[t2], %[b2], 0\n\t"
+            "s_cselect_b64 %[t3], %[b3], 0\n\t"
+            "s_or_b64 %[w0], %[w0], %[t0]\n\t"
+            "s_or_b64 %[w1], %[w1], %[t1]\n\t"
+            "s_or_b64 %[w2], %[w2], %[t2]\n\t"
+            "s_or_b64 %[w3], %[w3], %[t3]"
+            : [w0] "+s"(wave[0]), [w1] "+s"(wave[1]), [w2] "+s"(wave[2]), [w3] "+s"(wave[3]), [t0] "=&s"(t0),
+              [t1] "=&s"(t1), [t2] "=&s"(t2), [t3] "=&s"(t3)
+            : [f] "s"(f), [b0] "s"(bits[0]), [b1] "s"(bits[1]), [b2] "s"(bits[2]), [b3] "s"(bits[3])
+            : "scc");
+    }
+}
+
+// One-word tables: wave |= (n0 & k0) ? bits0 : 0, then the same for member 1.  The
+// lane-mask conjunction's own SCC (result != 0) feeds the 64-bit select, so a member
+// costs and + select + or on the scalar unit (the compiler's lowering: and, compare,
+// two 32-bit selects, or; C2 +1.6 % over it, profiles/r07a_scalar_diet_ab.txt).
+__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t n0, uint64_t k0, uint64_t bits0, uint64_t n1,
+                                            uint64_t k1, uint64_t bits1) {
+    uint64_t t;
+    asm("s_and_b64 %[t], %[n0], %[k0]\n\t"
+        "s_cselect_b64 %[t], %[b0], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]\n\t"
+        "s_and_b64 %[t], %[n1], %[k1]\n\t"
+        "s_cselect_b64 %[t], %[b1], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]"
+        : [w] "+&s"(wave), [t] "=&s"(t)
+        : [n0] "s"(n0), [k0] "s"(k0), [b0] "s"(bits0), [n1] "s"(n1), [k1] "s"(k1), [b1] "s"(bits1)
+        : "scc");
+}
+// (single lane masks: per-lane tables test no behind rule at the member level)
+__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t f0, uint64_t bits0, uint64_t f1, uint64_t bits1) {
+    uint64_t t;
+    asm("s_cmp_lg_u64 %[f0], 0\n\t"
+        "s_cselect_b64 %[t], %[b0], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]\n\t"
+        "s_cmp_lg_u64 %[f1], 0\n\t"
+        "s_cselect_b64 %[t], %[b1], 0\n\t"
+        "s_or_b64 %[w], %[w], %[t]"
+        : [w] "+&s"(wave), [t] "=&s"(t)
+        : [f0] "s"(f0), [b0] "s"(bits0), [f1] "s"(f1), [b1] "s"(bits1)
+        : "scc");
+}
+
+// an SGPR pointer the compiler cannot see through: loads through it stay where they are written
+__device__ __forceinline__ cv4f_t *opaque(cv4f_t *p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+// The per-lane thresholds of per-lane (REL) tables, both members of an entry
+// per packed FMA.  The constants sit in VGPR pairs (kc = {kClRel, kBehindRel},
+// kp = {kPfRel, kSlabRel}, aux = {slab_e0, |D.y|}) and op_sel broadcasts one
+// half to both lanes: an f32 FMA with a literal and an SGPR row lowered to
+// v_mov + v_fmamk, two VALU per threshold where this is half of one.  Every
+// value is the same single-rounded FMA as fmaf, so the bits are unchanged.
+struct ClConst {
+    f2 kc, kp, aux;
+};
+
+// A constant in a VGPR, written where the walk starts: a plain constant is
+// hoisted to the kernel's entry and held across every loop, which pushed other
+// values into scratch.
+__device__ __forceinline__ float walk_const(float c) {
+    float r;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(c));
+    return r;
+}
+
+// t = cc * kPfRel + r (a member pair's near-line thresholds)
+__device__ __forceinline__ f2 member_thr(f2 cc, const ClConst &k, f2 r) {
+    f2 t;
+    asm("v_pk_fma_f32 %[t], %[cc], %[kp], %[r] op_sel_hi:[1,0,1]" : [t] "=v"(t) : [cc] "v"(cc), [kp] "v"(k.kp), [r] "s"(r));
+    return t;
+}
+
+// A cluster pair's near-line thresholds t = cc kClRel + R, behind bounds
+// b = beta - cc kBehindRel, and the height-slab distance d = |O.y + D.y T - ymid|
+// (before the abs) with its limit thr = |D.y| srho + (yhalf + E),
+// E = cc kSlabRel + slab_e0 (cluster_pair below).
+__device__ __forceinline__ void cluster_thr(f2 cc, const ClConst &k, f2 r, f2 beta, f2 &t, f2 &b) {
+    asm("v_pk_fma_f32 %[t], %[cc], %[kc], %[r] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %[b], %[cc], %[kc], %[beta] op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]"
+        : [t] "=&v"(t), [b] "=&v"(b)
+        : [cc] "v"(cc), [kc] "v"(k.kc), [r] "s"(r), [beta] "s"(beta));
+}
+__device__ __forceinline__ void cluster_slab(f2 cc, f2 T, const RayPk &ray, const ClConst &k, f2 srho, f2 ymid,
+                                             f2 yhalf, f2 &d, f2 &thr) {
+    asm("v_pk_fma_f32 %[thr], %[cc], %[kp], %[aux] op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"
+        "v_pk_add_f32 %[thr], %[yhalf], %[thr]\n\t"
+        "v_pk_fma_f32 %[thr], %[aux], %[srho], %[thr] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[d], %[ry], %[T], %[ry] op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
+        "v_pk_add_f32 %[d], %[d], %[ymid] neg_lo:[0,1] neg_hi:[0,1]"
+        : [thr] "=&v"(thr), [d] "=&v"(d)
+        : [cc] "v"(cc), [kp] "v"(k.kp), [aux] "v"(k.aux), [yhalf] "s"(yhalf), [srho] "s"(srho), [ry] "v"(ray.y),
+          [T] "v"(T), [ymid] "s"(ymid));
+}
+
+template <int W, bool REL>
+__device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_t count, const RayPk &ray,
+                                             uint64_t (&wave)[kClWords], const ClConst &k, PfStats *ps) {
+    constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
+    if (ps) ps->groups += count;
+    // (the end offset opaque to the optimiser: it otherwise derives a trip count and runs a
+    // second, down-counting induction variable beside the offset -- one more SALU per entry)
+    uint32_t end = (first + count) * kEntryBytes;
+    asm volatile("" : "+s"(end));
+    for (uint32_t off = first * kEntryBytes; off != end; off += kEntryBytes) {
+        cv4f_t *e = cl_entry(ct, off);
+        const Rows4 rows = load_rows4(e);  // (one scalar load per entry)
+        const v4f_t r0 = rows.r0, r1 = rows.r1, r2 = rows.r2, r3 = rows.r3;
+        f2 T, cc;
+        const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
+        // a lane may hit the sphere: near the line, and not wholly behind the origin
+        const f2 tr = REL ? member_thr(cc, k, f2{r1.z, r1.w}) : f2{r1.z, r1.w};
+        const float t0 = tr.x, t1 = tr.y;
+        const float b0 = REL ? __builtin_fmaf(cc.x, -kBehindRel, r3.x) : r3.x;
+        const float b1 = REL ? __builtin_fmaf(cc.y, -kBehindRel, r3.y) : r3.y;
+        // Members of per-lane (REL) tables take the near-line test only: their behind
+        // threshold is a per-lane FMA, and the rule stays at the cluster level
+        // (RTWeekend +2.7 % same box; C2's scene-wide table loses 1.7 % without it).
+        // Either way a skipped pair is a proven miss.
+        constexpr bool kBehind = !REL;
+        const uint64_t n0m = __builtin_amdgcn_ballot_w64(!(v.x >= t0)), n1m = __builtin_amdgcn_ballot_w64(!(v.y >= t1));
+        if constexpr (W == 1) {
+            const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
+            const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
+            if constexpr (kBehind)
+                merge_word1(wave[0], n0m, __builtin_amdgcn_ballot_w64(!(T.x < b0)), w0, n1m,
+                            __builtin_amdgcn_ballot_w64(!(T.y < b1)), w1);
+            else
+                merge_word1(wave[0], n0m, w0, n1m, w1);
+        } else {
+            const uint64_t f0m = kBehind ? n0m & __builtin_amdgcn_ballot_w64(!(T.x < b0)) : n0m;
+            const uint64_t f1m = kBehind ? n1m & __builtin_amdgcn_ballot_w64(!(T.y < b1)) : n1m;
+            if constexpr (W == 2) {
+                uint64_t bw0[W], bw1[W];  // member 0 and 1 bits in word w
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const v4f_t rb = w == 0 ? r2 : e[3 + w];
+                    bw0[w] = (uint64_t)__float_as_uint(rb.x) | ((uint64_t)__float_as_uint(rb.y) << 32);
+                    bw1[w] = (uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32);
+                }
+                merge_words<W>(wave, f0m, bw0);
+                merge_words<W>(wave, f1m, bw1);
+            } else {
+                // four-word tables: a member's bit rows of words 1-3 are read only when some lane flagged it (a
+                // uniform branch), so they do not hold 12 SGPRs across every entry's prefilter (RTWeekend
+                // +0.7 %; the two-word form keeps its selects: C5 -0.5 % this way, profiles/r05u_lazy_bits_ab.txt);
+                // word 0's row came with the entry's one load
+                const bool f0 = f0m != 0, f1 = f1m != 0;
+                if (f0 | f1) {
+                    cv4f_t *eb = opaque(e);
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        const v4f_t rb = w == 0 ? r2 : eb[3 + w];
+                        if (f0) wave[w] |= (uint64_t)__float_as_uint(rb.x) | ((uint64_t)__float_as_uint(rb.y) << 32);
+                        if (f1) wave[w] |= (uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// One cluster-pair entry (both levels of the table share the row layout):
+// the wave's lanes that may reach cluster 0 / 1 (near the line, not wholly
+// behind the origin, and for per-lane tables inside the height slab).
+// Height slab (per-lane tables): the line's height over the t range that can
+// reach the cluster is c +- |D.y| srho with c = O.y + D.y T; it cannot meet a
+// member when that range clears [ymid - yhalf, ymid + yhalf] by the lane's
+// margin E (a ground-plane scene: rays leaving the ground cross the thin layer
+// of small spheres only near their origin).
+// (The sub-level slab and behind tests stay: without them RTWeekend -0.1 % and -3 %, profiles/r06n_slab_ab.txt.)
+template <bool REL>
+__device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const ClConst &k, uint64_t &m0,
+                                             uint64_t &m1, v4f_t &ranges) {
+    const Rows4 rows = load_rows4(e);  // (one scalar load per entry; row 2 = the entry's ranges)
+    const v4f_t r0 = rows.r0, r1 = rows.r1, r3 = rows.r3;
+    ranges = rows.r2;
+    f2 T, cc;
+    const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
+    if constexpr (REL) {
+        f2 t, b;
+        cluster_thr(cc, k, f2{r1.z, r1.w}, f2{r3.x, r3.y}, t, b);
+        m0 = ballot_and(!(v.x >= t.x), !(T.x < b.x));
+        m1 = ballot_and(!(v.y >= t.y), !(T.y < b.y));
+        const v4f_t r4 = e[4];
+        f2 d, thr;
+        cluster_slab(cc, T, ray, k, f2{r3.z, r3.w}, f2{r4.x, r4.y}, f2{r4.z, r4.w}, d, thr);
+        m0 &= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(d.x) > thr.x));
+        m1 &= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(d.y) > thr.y));
+    } else {
+        m0 = ballot_and(!(v.x >= r1.z), !(T.x < r3.x));
+        m1 = ballot_and(!(v.y >= r1.w), !(T.y < r3.y));
+    }
+}
+
+// ps (RTK_STATS): groups += member-pair entries tested, pairs += sphere pairs
+// rechecked exactly, lane_pairs += clusters entered (per wave, both levels),
+// cl_tested += cluster-pair entries tested (both levels), cl_top_entered += top
+// clusters entered (two-level tables).
+// Tables of two or more mask words (more than 32 groups) have two levels: a
+// top cluster's entry ranges index sub-cluster entries of a few spheres each,
+// whose ranges index the member entries (rt_host.cpp cluster_table); the bound
+// of a cluster covers every sphere under it, so a skipped top cluster skips
+// its sub-clusters' members too.
+template <bool SIMD, int W, bool GS, bool REL>
+__device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray,
+                                                 Hit &h, bool fast, PfStats *ps) {
+    cv4f_t *ct = (cv4f_t *)a.clusters;
+    uint64_t wave[kClWords] = {0ull, 0ull, 0ull, 0ull};
+    constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
+    constexpr bool kTwoLevels = W >= 2;
+    // per-lane part of the height-slab margin (REL tables; rt_host.cpp cluster_table)
+    const float oy = ray.y.x, dy = ray.y.y;
+    const float slab_e0 = REL ? __builtin_fmaf(__builtin_fabsf(oy), 0x1p-21f, kSlabRel) : 0.0f;
+    ClConst k;
+    if constexpr (REL) {
+        k.kc = f2{walk_const(kClRel), walk_const(kBehindRel)};
+        k.kp = f2{walk_const(kPfRel), walk_const(kSlabRel)};
+        k.aux = f2{slab_e0, __builtin_fabsf(dy)};
+    }
+    // the member pairs of an entered (sub-)cluster pair entry
+    auto members = [&](v4f_t r2, bool in0, bool in1) {
+        if (ps) ps->lane_pairs += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
+        if (in0) member_pairs<W, REL>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, wave, k, ps);
+        if (in1) member_pairs<W, REL>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, wave, k, ps);
+    };
+    // the sub-cluster pair entries [first, first + count) of an entered top cluster
+    auto subs = [&](uint32_t first, uint32_t count) {
+        if (ps) ps->cl_tested += count;
+        for (uint32_t off = first * kEntryBytes, end = (first + count) * kEntryBytes; off != end; off += kEntryBytes) {
+            cv4f_t *e = cl_entry(ct, off);
+            uint64_t m0, m1;
+            v4f_t r2;
+            cluster_pair<REL>(e, ray, k, m0, m1, r2);
+            members(r2, m0 != 0, m1 != 0);
+        }
+    };
+    if (ps) ps->cl_tested += a.n_cpairs;
+    // (every caller walks a table of at least one cluster-pair entry -- the run-time kernel tests
+    // n_cpairs, the walk kernels are launched with one only: no zero-trip test in front of the loop)
+    uint32_t off = 0;
+    const uint32_t end = a.n_cpairs * kEntryBytes;
+    do {
+        cv4f_t *e = cl_entry(ct, off);
+        uint64_t m0, m1;
+        v4f_t r2;
+        cluster_pair<REL>(e, ray, k, m0, m1, r2);
+        if constexpr (kTwoLevels) {
+            if (ps) ps->lane_pairs += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
+            if (ps) ps->cl_top_entered += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
+            if (m0 != 0) subs(__float_as_uint(r2.x), __float_as_uint(r2.y));
+            if (m1 != 0) subs(__float_as_uint(r2.z), __float_as_uint(r2.w));
+        } else {
+            members(r2, m0 != 0, m1 != 0);
+        }
+        off += kEntryBytes;
+    } while (off != end);
+    cv4f_t *gp = (cv4f_t *)a.groups;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        uint64_t m = wave[w];
+        while (m) {
+            const uint32_t q = (uint32_t)__builtin_ctzll(m) & ~1u;  // first pair of the lowest flagged group
+            const uint32_t g = 32u * (uint32_t)w + (q >> 1);
+            // (both flags from one shift, each a 32-bit bit test; the 64-bit tests of bits q and q + 1
+            // cost a shift, a mask and a 64-bit compare apiece on the scalar unit)
+            const uint32_t pp = (uint32_t)(m >> q);
+            const bool f01 = (pp & 1u) != 0u, f23 = (pp & 2u) != 0u;
+            m &= ~(3ull << q);
+            if (ps) ps->pairs += (f01 ? 1u : 0u) + (f23 ? 1u : 0u);
+            recheck_pairs<SIMD>(a, load_group_exact_at(gp + kGroupF4 * g), g, ray, h, fast, f01, f23);
+        }
+    }
+}
+
+// All four spheres of group g; one wave-level branch per group, nested
+// branches only for the (rare) lanes that pass the distance test.
+template <bool SIMD>
+__device__ __forceinline__ void test_group(const TraceArgs &a, const Group &G, uint32_t g, const RayPk &p, Hit &h, bool fast,
+                                           uint32_t *hit_groups) {
+    f2 T01, T23;
+    const f2 d01 = pair_dist(p, f2{G.x[0], G.x[1]}, f2{G.y[0], G.y[1]}, f2{G.z[0], G.z[1]}, T01);
+    const f2 d23 = pair_dist(p, f2{G.x[2], G.x[3]}, f2{G.y[2], G.y[3]}, f2{G.z[2], G.z[3]}, T23);
+    bool h0, h1, h2, h3;
+    if (SIMD) {  // HitMask = d < r^2 (main.cpp:409)
+        h0 = d01.x < G.r2[0];
+        h1 = d01.y < G.r2[1];
+        h2 = d23.x < G.r2[2];
+        h3 = d23.y < G.r2[3];
+    } else {  // !(d > r^2) over the Count real spheres only (main.cpp:547,557)
+        const uint32_t s0 = 4u * g;
+        h0 = s0 + 0u < a.n_spheres && !(d01.x > G.r2[0]);
+        h1 = s0 + 1u < a.n_spheres && !(d01.y > G.r2[1]);
+        h2 = s0 + 2u < a.n_spheres && !(d23.x > G.r2[2]);
+        h3 = s0 + 3u < a.n_spheres && !(d23.y > G.r2[3]);
+    }
+    if (hit_groups && __ballot(h0 | h1 | h2 | h3)) *hit_groups += 1;
+    if (h0 | h1 | h2 | h3) {
+        if (h0) candidate<SIMD, 0>(h, g, T01.x, d01.x, G.r2[0], fast);
+        if (h1) candidate<SIMD, 1>(h, g, T01.y, d01.y, G.r2[1], fast);
+        if (h2) candidate<SIMD, 2>(h, g, T23.x, d23.x, G.r2[2], fast);
+        if (h3) candidate<SIMD, 3>(h, g, T23.y, d23.y, G.r2[3], fast);
+    }
+}
+
+// pair_dist for rays that all start at the camera (primary rounds): C = S - O
+// is the same on every lane, so its three packed subtractions come from the
+// cull pass's table (TraceArgs.prim, computed with the same single f32
+// rounding) and the C operands stay in SGPRs -- 16 packed ops instead of 19.
+__device__ __forceinline__ f2 pair_dist_c(const RayPk &r, f2 cx, f2 cy, f2 cz, f2 &T) {
+    f2 qx, qy, qz, t, d;
+    asm("v_pk_mul_f32 %[t], %[cx], %[rx] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_mul_f32 %[d], %[cy], %[ry] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[T], %[t], %[d]\n\t"
+        "v_pk_mul_f32 %[t], %[cz], %[rz] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[T], %[T], %[t]\n\t"
+        "v_pk_mul_f32 %[t], %[rx], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[qx], %[cx], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[t], %[ry], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[qy], %[cy], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[t], %[rz], %[T] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %[qz], %[cz], %[t] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %[d], %[qx], %[qx]\n\t"
+        "v_pk_mul_f32 %[t], %[qy], %[qy]\n\t"
+        "v_pk_add_f32 %[d], %[d], %[t]\n\t"
+        "v_pk_mul_f32 %[t], %[qz], %[qz]\n\t"
+        "v_pk_add_f32 %[d], %[d], %[t]"
+        : [qx] "=&v"(qx), [qy] "=&v"(qy), [qz] "=&v"(qz), [t] "=&v"(t), [T] "=&v"(T), [d] "=&v"(d)
+        : [cx] "s"(cx), [cy] "s"(cy), [cz] "s"(cz), [rx] "v"(r.x), [ry] "v"(r.y), [rz] "v"(r.z));
+    return d;
+}
+
+// One sphere pair of a primary round (spheres L0, L0 + 1 of group g, camera-relative rows from
+// TraceArgs.prim): test_group's two halves as separate pair tests.
+template <bool SIMD, int L0>
+__device__ __forceinline__ void test_half_prim(const TraceArgs &a, uint32_t g, const RayPk &p, Hit &h, bool fast, f2 cx, f2 cy,
+                                               f2 cz, float r2a, float r2b) {
+    f2 T;
+    const f2 d = pair_dist_c(p, cx, cy, cz, T);
+    bool ha, hb;
+    if (SIMD) {  // HitMask = d < r^2 (main.cpp:409)
+        ha = d.x < r2a;
+        hb = d.y < r2b;
+    } else {  // !(d > r^2) over the Count real spheres only (main.cpp:547,557)
+        const uint32_t s0 = 4u * g + (uint32_t)L0;
+        ha = s0 < a.n_spheres && !(d.x > r2a);
+        hb = s0 + 1u < a.n_spheres && !(d.y > r2b);
+    }
+    if (ha | hb) {
+        if (ha) candidate<SIMD, L0>(h, g, T.x, d.x, r2a, fast);
+        if (hb) candidate<SIMD, L0 + 1>(h, g, T.y, d.y, r2b, fast);
+    }
+}
+
+// Pair pr of a primary round's pair mask (half pr & 1 of group pr >> 1); the mask's pairs come in
+// ascending order, the reference's sphere order, so the per-class minima and tie rules are those of
+// the full group loop.
+template <bool SIMD>
+__device__ __forceinline__ void test_pair_prim(const TraceArgs &a, cv4f_t *prim, uint32_t pr, const RayPk &p, Hit &h, bool fast) {
+    const uint32_t g = pr >> 1;
+    cv4f_t *pg = prim + kPrimF4 * g;
+    const v4f_t cx = pg[0], cy = pg[1], cz = pg[2], r2 = pg[3];
+    if (pr & 1u) test_half_prim<SIMD, 2>(a, g, p, h, fast, f2{cx.z, cx.w}, f2{cy.z, cy.w}, f2{cz.z, cz.w}, r2.z, r2.w);
+    else test_half_prim<SIMD, 0>(a, g, p, h, fast, f2{cx.x, cx.y}, f2{cy.x, cy.y}, f2{cz.x, cz.y}, r2.x, r2.y);
+}
+
+}  // namespace rtk

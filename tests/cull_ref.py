@@ -1,5 +1,5 @@
 """CPU restatement (numpy, f64) of the cull pass's primary masks
-(rt_kernel.hip tile_cone / cone_may_hit / wave_tile_mask), SIMD rule set,
+(rt_sched.hip tile_cone / cone_may_hit / wave_tile_mask), SIMD rule set,
 one band: one bit per sphere pair (bit p: sphere slots 2p, 2p + 1), one u64
 word per 64 pairs per wave tile, word ((tile * 4 + wave) * n_words + w),
 n_words = ceil(2 groups / 64) (rt_kernel.h rtk_mask_words).  Test helper

@@ -1,4 +1,4 @@
-"""CPU check of the primary-ray cull proof (rt_kernel.hip
+"""CPU check of the primary-ray cull proof (rt_sched.hip
 cone_may_hit): every sphere pair a pixel's primary rays can reach (f64 line
 test over a jitter grid) is in its wave tile's pair mask, as the numpy
 restatement of the cull pass computes it.  test_gpu_parity.py pins the GPU's masks to the

@@ -64,7 +64,7 @@ def _random_mean(n, seed):
 
 
 def _walk_kernel_ran(info):
-    """The launch shape has walk-specialised kernels (rt_kernel.hip launch_p)."""
+    """The launch shape has walk-specialised kernels (rt_kernel.h rtk_walk_shape)."""
     return info["PixelsPerLane"] == 4 or info["LanesPerPixel"] in (4, 8, 16)
 
 

@@ -508,7 +508,7 @@ def test_dead_tiles_fold_a_nonzero_running_mean(rt, orc, torch_cuda, gdev):
 def test_running_mean_weights_at_large_previous_counts(rt, orc, torch_cuda, prev_count, P):
     """The fold weights RN(1/(f32)(n)) and RN((f32)(n-1)/(f32)(n)) (main.cpp:484-487)
     come from the device's static table of the first 65,536 frames (TraceArgs.weights)
-    and past it from rcp_rn / div_rn (rt_kernel.hip fold_weights) in the one-wave
+    and past it from rcp_rn / div_rn (rtk_math.h fold_weights) in the one-wave
     kernels: launches across the table's end, frames far past it, counts whose f32
     conversion rounds (> 2^24) and the top of the u32 range, against the oracle's IEEE
     divisions, with a random non-zero running mean, every lane shape's blend path."""

@@ -28,7 +28,7 @@ def exact_dist(cx, cy, cz, dx, dy, dz):
 
 
 def prefilter(cx, cy, cz, dx, dy, dz, with_t=False, with_cc=False):
-    """rt_kernel.hip pair_prefilter, lane by lane: e (and its FMA T, and cc = |C|^2)."""
+    """rtk_walk.h pair_prefilter, lane by lane: e (and its FMA T, and cc = |C|^2)."""
     cc = fma(cx, cx, fma(cy, cy, cz * cz))
     T = fma(cz, dz, fma(cy, dy, cx * dx))
     e = fma(-T, T, cc)
@@ -37,16 +37,16 @@ def prefilter(cx, cy, cz, dx, dy, dz, with_t=False, with_cc=False):
     return (e, T) if with_t else e
 
 
-PF_REL = F(2.0 ** -15)  # rt_kernel.hip kPfRel
+PF_REL = F(2.0 ** -15)  # rtk_walk.h kPfRel
 
 
-CL_REL = F(9.2e-4)            # rt_kernel.hip kClRel
-BEHIND_REL = F(4.5 * 2.0 ** -24)  # rt_kernel.hip kBehindRel
+CL_REL = F(9.2e-4)            # rtk_walk.h kClRel
+BEHIND_REL = F(4.5 * 2.0 ** -24)  # rtk_walk.h kBehindRel
 SLAB_REL = F(2.0 ** -9)       # rt_kernel.h kSlabRel
 
 
 def slab_skip(tc, cc, oy, dy, srho, ymid, yhalf):
-    """rt_kernel.hip clustered_groups, per-lane tables: the height-slab test skips a
+    """rtk_walk.h clustered_groups, per-lane tables: the height-slab test skips a
     cluster when |RN(fma(D.y, T, O.y)) - ymid| > RN(fma(|D.y|, srho, yhalf + E)),
     E = RN(fma(cc, kSlabRel, RN(fma(|O.y|, 2^-21, kSlabRel))))."""
     with np.errstate(invalid="ignore", over="ignore"):
@@ -196,7 +196,7 @@ def test_short_sqrt_flag_follows_the_radius_range(rt):
 @pytest.mark.parametrize("idx,n_spheres", [(1, 64), (1, 37), (1, 16), (1, 100), (1, 256), (0, None), (2, None)])
 @pytest.mark.parametrize("simd", [True, False])
 def test_cluster_prefilter_never_skips_an_exact_hit(rt, idx, n_spheres, simd):
-    """The clustered loop (rt_kernel.hip clustered_groups) skips every member
+    """The clustered loop (rtk_walk.h clustered_groups) skips every member
     of a cluster when e_c >= rc2p_c on all lanes; the members of a tested
     cluster are flagged by their own r2p.  Every exact hit must survive both
     levels, and every hittable sphere must be a member of exactly one cluster."""
@@ -216,7 +216,7 @@ def check_clusters(rt, scene, simd, seed, require_culls=False, n_rays=4000):
     r2, r2p, flags = rt.scene_prefilter(scene, simd)
     if ncp == 0:
         return 0, 0
-    relative = bool(flags & 4)  # per-lane thresholds (rt_kernel.hip kClRel / kPfRel / kBehindRel)
+    relative = bool(flags & 4)  # per-lane thresholds (rtk_walk.h kClRel / kPfRel / kBehindRel)
     centres, radius = slot_spheres(rt, scene, simd)
     live = np.isfinite(r2p)
     # decode the table: clusters -> member spheres (by centre and r2p) and pair indices;

@@ -3,7 +3,7 @@ reference; RT_FLAG_SRGB_POW) on the CPU.
 
 The reference's powf is libm's (musl in its WASM build, glibc here: the same
 algorithm, not correctly rounded).  The kernel takes the f64 pow rounded once
-to f32 (rt_kernel.hip linear_to_srgb_pow).  These tests pin that choice
+to f32 (rtk_math.h linear_to_srgb_pow).  These tests pin that choice
 exhaustively over every f32 the branch sees, [0.0031308, 1]: the f32 values may
 differ in the last bit, the RGBA8 bytes never do.  The GPU's own bytes are
 checked against the oracle over the same inputs in
@@ -27,7 +27,7 @@ def u8(v: np.ndarray) -> np.ndarray:
 
 
 def kernel_model(L: np.ndarray) -> np.ndarray:
-    """rt_kernel.hip linear_to_srgb_pow, op for op (f64 pow, f32 rest, unfused)."""
+    """rtk_math.h linear_to_srgb_pow, op for op (f64 pow, f32 rest, unfused)."""
     p = np.power(L.astype(np.float64), Y).astype(F)
     return F(1.055) * p - F(0.055)
 
