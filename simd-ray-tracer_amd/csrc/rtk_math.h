@@ -253,7 +253,9 @@ __device__ __forceinline__ void start_sample(const Args &a, uint32_t x, uint32_t
     p.bounce = 0;
 }
 
-// Emission, attenuation and the next direction (main.cpp:446-481).
+// Emission, attenuation and the next direction (main.cpp:446-481).  A hit at the bounce limit
+// takes the emission term alone: trace_kernel restates the first three statements for it, and
+// they must stay the same operations on the same operands there and here.
 __device__ __forceinline__ void shade(const Lut &lut, float4 col_spec, float4 emis_ior, const float4 *diel, float hx,
                                       float hy, float hz, bool inside, Sample &p) {
     p.cx = p.cx + emis_ior.x * p.ax;

@@ -12,7 +12,8 @@
 // Exactness: rtk_math.h.
 //
 // Work shape: lanes alternate between starting primary rays
-// and gathering secondary segments; primary rays test only the sphere groups
+// and gathering secondary segments (a hit is shaded at the start of the segment
+// it feeds: the trip loop's comment); primary rays test only the sphere groups
 // their tile's cone can reach (tiles whose cone reaches none fold their
 // samples without tracing); secondary rays run an FMA prefilter with a proven
 // error bound and re-test exactly only the sphere pairs it flags.  Sphere
@@ -80,6 +81,9 @@ struct TraceStats<true> {
         cyc_sync = t_sync - t_cull;
         cyc_post = now() - t_sync;
     }
+    // A traced trip's cycles go to the kind of its round.  The shade of a hit runs at the start of the
+    // round that continues the path, so cyc_sec holds every shade with the walk (merged rounds: cyc_pri,
+    // as all of their trips), and cyc_pri is sample start, pair tests, hit select and the park alone.
     __device__ __forceinline__ void trip_begin() { t_trip = now(); }
     __device__ __forceinline__ void trip_end(bool traced, uint32_t do_sec) {
         const uint64_t t = now();
@@ -355,7 +359,8 @@ void trace_kernel(TraceArgs a) {
 
     // owner lanes of in-image pixels (they fold until every frame is folded)
     const uint64_t folding = ballot_and(owner, valid);
-    // lane mode: 0 = next sample pending, 1 = path continues (secondary), 2 = no samples left
+    // lane mode: 0 = next sample pending, 1 = path continues (a pending hit to shade, then its secondary
+    // segment), 2 = no samples left
     // The P lanes of a pixel take its samples in order as they free up (kDynamic):
     // each trip the lanes wanting a sample are ranked inside the slice and take
     // next, next + 1, ...  A lane whose samples run short no longer idles while its
@@ -420,6 +425,13 @@ void trace_kernel(TraceArgs a) {
     }
 
     st.post_end();
+    // A mode-1 lane's pending hit: the accepted hit of the segment p still describes (its tmin, and
+    // the sphere index with the inside flag in bit 31), shaded at the start of the lane's next round.
+    // Read only in mode 1 and written on every way into it, so a lane that finishes a sample (or a
+    // Q > 1 lane moving to its next pixel slot) carries none over.
+    constexpr uint32_t kPendInside = 0x80000000u;
+    float pend_t = 0.0f;
+    uint32_t pend_s = 0u;
     // Re-derive the winner's HitNormal / NextRayOrigin exactly as they were
     // formed at acceptance (main.cpp:423-429), then shade and bounce.
     auto shade_hit = [&](float tmin, uint32_t sidx, bool inside) {
@@ -520,6 +532,22 @@ void trace_kernel(TraceArgs a) {
             folded += 1u;
         }
     };
+    // The trip loop.  A hit is shaded at the start of the segment it feeds, not at the end of the one
+    // that found it: a lane whose segment hit and whose path goes on keeps p as it was for that
+    // segment, notes the hit (pend_t, pend_s) and turns to mode 1; the round that next traces the
+    // lane first runs shade_hit on the note.  The lanes of a secondary round are exactly the lanes
+    // with such a note, so the shade block is issued in secondary rounds only, for all of the round's
+    // lanes; primary rounds (about 83 % of their lanes hit) issue none, and secondary rounds no
+    // longer issue one for the fifth of their lanes that hit.  Rounds, their lanes and their order
+    // are what they were, trip for trip: nothing in the header looks at anything the shade writes.
+    // Exactness: per lane the f32 operations, table gathers and PCG draws of a path are the same, in
+    // the same order on the same values -- shade_hit reads only the lane's own p and the hit, and
+    // between the hit and its shade the lane takes part in no round.  Only the wave-level moment of
+    // the shade moves, and no result depends on it.  The one place that is not the same code is a hit
+    // at the bounce limit, which feeds no segment: it takes shade's emission term alone (its first
+    // three statements, on the attenuation before the colour multiplies it: same operands, same
+    // order, unfused) and ends the path; the normal, draws and direction it skips reached nothing
+    // (the sample's RNG state and ray die with it).
     for (;;) {
         // ring space: sample k may start once k < folded + kRing (the oldest
         // unfolded sample's lane is never blocked, so this cannot deadlock)
@@ -584,7 +612,12 @@ void trace_kernel(TraceArgs a) {
             if (bounces) nrays += (uint32_t)__builtin_popcountll(round);
             if (__builtin_amdgcn_inverse_ballot_w64(round)) {  // (the mask itself becomes exec)
                 pseg += 1u;
-                if (!do_sec && mode == 0u) start_sample(kernel_args(), x, y, a.prev_count + k, p);
+                // The round's lanes are in mode 1 (a pending hit to shade) or 0 (a sample to start).  Split
+                // rounds hold one kind, so the choice is the round's own; merged rounds hold both.
+                if (kMergeable ? mode == 1u : do_sec != 0u)
+                    shade_hit(pend_t, pend_s & ~kPendInside, (pend_s & kPendInside) != 0u);
+                else
+                    start_sample(kernel_args(), x, y, a.prev_count + k, p);
                 bool done;
                 if (!bounces) {
                     done = true;  // no segment is traced; the frame folds black
@@ -677,9 +710,18 @@ void trace_kernel(TraceArgs a) {
                             p.cz = p.cz + (w + s * 1.0f) * p.az;
                         }
                         done = true;
+                    } else if (p.bounce + 1u == a.max_bounce) {
+                        // a hit at the bounce limit: its emission term is all that reaches the output
+                        // (shade's first three statements, main.cpp:446-448)
+                        const float4 ei = mat_src[kSphereF4 * sidx + 2u];
+                        p.cx = p.cx + ei.x * p.ax;
+                        p.cy = p.cy + ei.y * p.ay;
+                        p.cz = p.cz + ei.z * p.az;
+                        done = true;
                     } else {
-                        shade_hit(tmin, sidx, inside);
-                        done = p.bounce == a.max_bounce;
+                        pend_t = tmin;
+                        pend_s = sidx | (inside ? kPendInside : 0u);
+                        done = false;
                     }
                 }
                 if (done) {
