@@ -271,6 +271,48 @@ uint32_t rt_band_local_rows(uint32_t height, uint32_t band_rows, uint32_t band_c
 int rt_trace(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
              uint64_t *d_rays, void *stream);
 
+/* The reference hands its workers 32 x 32 tiles: WorkQueueStart(RenderTile, TilesX*TilesY, ..)
+ * gives each a WorkEntry, RenderTile turns it into TileX = Tile % TilesX, TileY = Tile / TilesX
+ * and clips the tile to the image (main.cpp:9, 362-368, 851-856). */
+#define RT_TILE_SIZE 32u   /* TileSize, main.cpp:9 */
+/* TilesX*TilesY of a width x height image as OnRender forms them (ceil division);
+ * *out_tiles_x (optional) = TilesX.  0 for an empty or oversized (> 65536) image. */
+uint32_t rt_tile_count(uint32_t width, uint32_t height, uint32_t *out_tiles_x);
+
+/* rt_trace over the listed tiles only: the caller's own tile queue, part of a frame, more
+ * samples for some tiles than for others, or the one tile that holds a pixel in question.
+ * tiles: HOST array of n_tiles WorkEntry values, Tile = TileY*TilesX + TileX with
+ * TilesX = ceil(Width/32), each tile clipped to the image as main.cpp:362-368 does.  Any order.
+ *  - Every pixel of a listed tile receives exactly the running mean and RGBA8 that rt_trace with
+ *    the same desc writes for it (a pixel's seeds, samples and fold never depend on what else
+ *    a launch traces).  No byte of any other pixel of CurrentImage or PreviousImage is written.
+ *  - Both images are the full Width x Height device images, as for rt_trace with one band.
+ *    BandCount must be 0 or 1 and BandIndex 0 (RT_EINVAL otherwise); BandRows is accepted as for
+ *    rt_trace; cam->TilesX is not read (rt_trace does not read it either).
+ *  - *d_rays grows by the bounce segments of the listed tiles' pixels only, traced ones and those
+ *    counted analytically (dead tiles).  A list naming every tile gives rt_trace's bits and count.
+ *  - PreviousRayCount is per call, as for rt_trace: frame k's seeds and weights depend on
+ *    PreviousRayCount + k only, so a caller whose tiles carry different sample counts keeps one
+ *    count per tile and lists together the tiles that share one.
+ *  - RT_EINVAL, before anything is enqueued: tiles == NULL with n_tiles > 0, an index >=
+ *    rt_tile_count(Width, Height), an index named twice (the reference's queue would fold that
+ *    tile twice; the library refuses rather than guess), and everything rt_trace refuses.
+ *    n_tiles == 0 or Frames == 0: RT_OK, nothing enqueued.
+ *  - The host array is consumed before the call returns: free or overwrite it at once.
+ *  - The selection is part of the launch key (camera, scene, geometry, lanes per pixel, list --
+ *    compared by content): the same list again reuses the cull masks, tile order and pixel
+ *    permutation; a different list is a new key and pays a cull pass, the first-launch split
+ *    and a fresh order.  Only the last key is kept.
+ *  - With rt_device_options LanesPerPixel left at its default, the lanes per pixel follow the
+ *    listed tiles' (clipped) pixel count per CU, not the frame's: a small window runs at 16 lanes
+ *    per pixel, as a small rank share does.
+ *  - Asynchronous on `stream` exactly like rt_trace; the host waits where rt_trace would (stream
+ *    switch, buffer growth) and in one more place: a new list is uploaded from one of two pinned
+ *    staging slots the library owns, and the call waits for a slot's previous upload (two new
+ *    lists earlier) if that copy has not finished yet. */
+int rt_trace_tiles(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
+                   const uint32_t *tiles, uint32_t n_tiles, uint64_t *d_rays, void *stream);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call
@@ -319,6 +361,11 @@ typedef struct rt_trace_info {
     uint32_t BufferGrowths;   /* launch-buffer (re)allocations on this device
                                  so far (tile lists, cull masks): constant
                                  across launches that rt_device_reserve covers */
+    uint32_t TilesSelected;   /* block tiles inside the tiles rt_trace_tiles listed
+                                 (== TilesTotal after rt_trace).  TilesTotal stays
+                                 the geometry's block tiles; TilesTraced counts the
+                                 live tiles among the selected, SegmentsFolded the
+                                 dead selected tiles' segments only             */
 } rt_trace_info;
 int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
 
@@ -331,7 +378,9 @@ int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
  * width times the largest height).  Masks are sized for the current scene;
  * rt_scene_upload re-applies the reservation for a larger one (if that fails,
  * the upload still succeeds and the reservation is dropped: later launches
- * grow their buffers as they need).  Waits for the device.  (New; the reference's arena is sized once in OnInit,
+ * grow their buffers as they need).  Also sizes what rt_trace_tiles needs for
+ * a width x local_rows image (the selection bitmap and its pinned staging).
+ * Waits for the device.  (New; the reference's arena is sized once in OnInit,
  * main.cpp:658.) */
 int rt_device_reserve(rt_device *dev, uint32_t width, uint32_t local_rows);
 
@@ -500,6 +549,8 @@ int64_t rt_debug_wave_times(rt_device *dev, uint64_t *out, uint64_t max_waves);
  * per sphere pair (bit p: spheres 2p and 2p + 1, i.e. half p & 1 of group
  * p >> 1): word ((tile * 4 + wave) * n_words + w), n_words = ceil(2 groups / 64).
  * Returns the number of words copied (0 when no cull pass ran), < 0 on error.
+ * After rt_trace_tiles the words of block tiles outside the listed tiles are
+ * unspecified (the cull pass leaves such a tile before it writes any).
  * Test hook: tests/test_gpu_parity.py checks them against a CPU restatement. */
 int64_t rt_debug_masks(rt_device *dev, uint64_t *out, uint64_t max_words);
 

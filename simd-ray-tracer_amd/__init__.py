@@ -91,7 +91,8 @@ class RtTraceDesc(ctypes.Structure):
 class RtTraceInfo(ctypes.Structure):  # rt_trace_last_info
     _fields_ = [("SegmentsFolded", c_uint64)] + [(n, c_uint32) for n in (
         "LanesPerPixel", "TilesTotal", "TilesTraced", "CullPassRan", "OrderedLaunches", "ClusteredWalk",
-        "GroupsPerRuleSet", "SplitHeadFrames", "OneWaveGroups", "Walk", "PixelsPerLane", "PixelsSorted", "BufferGrowths")]
+        "GroupsPerRuleSet", "SplitHeadFrames", "OneWaveGroups", "Walk", "PixelsPerLane", "PixelsSorted", "BufferGrowths",
+        "TilesSelected")]
 
 
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
@@ -168,6 +169,9 @@ SIGNATURES = {
     "rt_scene_upload": (c_int, [c_void_p, POINTER(RtScene)]),
     "rt_band_local_rows": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32]),
     "rt_trace": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_void_p]),
+    "rt_tile_count": (c_uint32, [c_uint32, c_uint32, POINTER(c_uint32)]),
+    "rt_trace_tiles": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32, c_void_p,
+                               c_void_p]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -323,6 +327,28 @@ def band_local_rows(height: int, band_rows: int, band_count: int, band_index: in
     return int(lib().rt_band_local_rows(height, band_rows, band_count, band_index))
 
 
+RT_TILE_SIZE = 32  # the reference's TileSize (main.cpp:9)
+
+
+def tile_count(width: int, height: int) -> int:
+    """TilesX * TilesY of a width x height image as OnRender forms its 32 x 32 tiles
+    (rt_tile_count; TilesX = ceil(width / 32)); 0 for an empty or oversized image."""
+    return int(lib().rt_tile_count(width, height, None))
+
+
+def tiles_of_rect(width: int, height: int, x0: int, y0: int, x1: int, y1: int) -> list:
+    """The tiles (Tile = TileY * TilesX + TileX, ascending) of a width x height image that the pixel
+    rectangle [x0, x1) x [y0, y1) touches, clipped to the image; [] when it covers no pixel.
+    Pure Python (no library call)."""
+    x0, y0, x1, y1 = max(0, int(x0)), max(0, int(y0)), min(int(width), int(x1)), min(int(height), int(y1))
+    if x0 >= x1 or y0 >= y1:
+        return []
+    tiles_x = (width + RT_TILE_SIZE - 1) // RT_TILE_SIZE
+    return [ty * tiles_x + tx
+            for ty in range(y0 // RT_TILE_SIZE, (y1 - 1) // RT_TILE_SIZE + 1)
+            for tx in range(x0 // RT_TILE_SIZE, (x1 - 1) // RT_TILE_SIZE + 1)]
+
+
 def scene_prefilter(scene: RtScene, simd: bool = True):
     """(r2, r2p, flags) per sphere slot 4*group+lane as rt_scene_upload packs
     them: the exact test's r^2, the secondary-ray prefilter threshold, and
@@ -429,6 +455,29 @@ class Device:
                         (RT_FLAG_ACCUM_ZERO if accum_zero else 0) | (RT_FLAG_SRGB_POW if srgb_pow else 0))
         _check(lib().rt_trace(self.handle, ctypes.byref(c), ctypes.byref(d), c_void_p(rays_ptr),
                               c_void_p(stream or 0)), "rt_trace")
+
+    def trace_tiles(self, cam: RtCameraInfo, *, tiles, width: int, height: int, prev_ptr: int, cur_ptr: int,
+                    rays_ptr: int, prev_count: int = 0, frames: int = 1, max_bounce: int = 5, simd: bool = True,
+                    band_rows: int = 32, accum_zero: bool = False, srgb_pow: bool = False,
+                    stream: Optional[int] = None) -> None:
+        """trace() over the listed 32 x 32 tiles only (rt_trace_tiles): `tiles` is any sequence of
+        integers Tile = TileY * TilesX + TileX (tiles_of_rect lists those of a pixel rectangle); the
+        images are the full width x height ones and no pixel outside the listed tiles is written.
+        The list is consumed before the call returns."""
+        t = np.ascontiguousarray(np.asarray(list(tiles) if not isinstance(tiles, np.ndarray) else tiles).reshape(-1))
+        if t.size and (t.dtype.kind not in "iu" or int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+            raise ValueError("tiles: a sequence of tile indices (non-negative integers)")
+        t = t.astype(np.uint32)
+        c = RtCameraInfo()
+        ctypes.pointer(c)[0] = cam
+        c.CurrentImage = RtImage(cur_ptr, width, height, RT_FORMAT_R8G8B8A8_U32)
+        c.PreviousImage = RtImage(prev_ptr, width, height, RT_FORMAT_R32B32G32A32_F32)
+        d = RtTraceDesc(width, height, prev_count, frames, max_bounce, 1 if simd else 0, RT_SEED_PIXEL,
+                        band_rows, 1, 0,
+                        (RT_FLAG_ACCUM_ZERO if accum_zero else 0) | (RT_FLAG_SRGB_POW if srgb_pow else 0))
+        _check(lib().rt_trace_tiles(self.handle, ctypes.byref(c), ctypes.byref(d),
+                                    c_void_p(t.ctypes.data if t.size else None), int(t.size), c_void_p(rays_ptr),
+                                    c_void_p(stream or 0)), "rt_trace_tiles")
 
     def last_info(self) -> dict:
         """What the last trace launched (rt_trace_last_info): segments counted

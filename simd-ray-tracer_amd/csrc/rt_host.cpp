@@ -118,6 +118,18 @@ struct rt_device {
     bool counts_known = true;
     unsigned long long *h_counts = nullptr;  // pinned {live tiles, dead pixels}
     hipEvent_t ev_counts = nullptr;
+    // rt_trace_tiles: the selection bitmap of the current tile key on the device (TraceArgs.sel; its
+    // words are part of tile_key, so keys compare by the lists' content).  A new key's bitmap is
+    // uploaded from one of two pinned slots, each guarded by an event recorded after its copy: a
+    // slot is rewritten only once that copy has finished (sel_upload)
+    uint32_t *d_sel = nullptr;
+    uint32_t *h_sel[2] = {nullptr, nullptr};
+    hipEvent_t ev_sel[2] = {nullptr, nullptr};
+    bool sel_in_flight[2] = {false, false};
+    uint32_t sel_slot = 0;
+    size_t sel_cap = 0;              // words of d_sel and of each pinned slot
+    size_t reserve_sel_words = 0;    // rt_device_reserve: the most bitmap words of any geometry reserved
+    std::vector<uint32_t> sel_bits;  // rt_trace_tiles builds the call's bitmap here (no allocation per call)
     uint64_t scene_gen = 0;  // bumped by every rt_scene_upload
     // the last stream rt_trace ran on (a switch waits for the device: below)
     hipStream_t tile_stream = nullptr;
@@ -311,6 +323,11 @@ extern "C" int rt_device_destroy(rt_device *d) {
     (void)hipFree(d->d_masks);
     (void)hipFree(d->d_pix_perm);
     (void)hipFree(d->d_pix_cost);
+    (void)hipFree(d->d_sel);
+    for (int i = 0; i < 2; ++i) {
+        if (d->h_sel[i]) (void)hipHostFree(d->h_sel[i]);
+        if (d->ev_sel[i]) (void)hipEventDestroy(d->ev_sel[i]);
+    }
     if (d->h_counts) (void)hipHostFree(d->h_counts);
     if (d->ev_counts) (void)hipEventDestroy(d->ev_counts);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -1121,6 +1138,48 @@ static int ensure_pixel_sort(rt_device *d, uint32_t n_tiles, size_t pixels, hipS
     return RT_OK;
 }
 
+// rt_trace_tiles' selection bitmap of `words` words: the device copy and the two pinned slots a
+// new key's bitmap is uploaded from.  Growing waits first, as above (a copy out of a slot is work
+// of that stream too), so no slot is in flight afterwards.
+static int ensure_sel(rt_device *d, size_t words, hipStream_t sync, bool device_wide) {
+    if (words <= d->sel_cap) return RT_OK;
+    if (device_wide) HIP_OK(hipDeviceSynchronize());
+    else HIP_OK(hipStreamSynchronize(sync));
+    (void)hipFree(d->d_sel);
+    d->d_sel = nullptr;
+    d->sel_cap = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (d->h_sel[i]) (void)hipHostFree(d->h_sel[i]);
+        d->h_sel[i] = nullptr;
+        d->sel_in_flight[i] = false;
+        if (!d->ev_sel[i] && hipEventCreateWithFlags(&d->ev_sel[i], hipEventDisableTiming) != hipSuccess)
+            return fail(RT_ENOMEM, "rt_trace_tiles: selection upload event");
+    }
+    if (hipMalloc(&d->d_sel, words * 4u) != hipSuccess ||
+        hipHostMalloc(&d->h_sel[0], words * 4u, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(&d->h_sel[1], words * 4u, hipHostMallocDefault) != hipSuccess)
+        return fail(RT_ENOMEM, "rt_trace_tiles: selection bitmap");
+    d->sel_cap = words;
+    d->last.BufferGrowths += 1;
+    d->tile_key.clear();
+    return RT_OK;
+}
+
+// A new key's bitmap -> d_sel on `s`, through the pinned slot not used last.  The slot's previous
+// copy (two different lists ago) has normally finished long since; if not, the host waits for it
+// here -- the one place rt_trace_tiles may block beyond rt_trace's own.
+static int sel_upload(rt_device *d, const uint32_t *bits, size_t words, hipStream_t s) {
+    const uint32_t slot = d->sel_slot ^ 1u;
+    if (d->sel_in_flight[slot]) HIP_OK(hipEventSynchronize(d->ev_sel[slot]));
+    d->sel_in_flight[slot] = false;
+    memcpy(d->h_sel[slot], bits, words * 4u);
+    HIP_OK(hipMemcpyAsync(d->d_sel, d->h_sel[slot], words * 4u, hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(d->ev_sel[slot], s));
+    d->sel_in_flight[slot] = true;
+    d->sel_slot = slot;
+    return RT_OK;
+}
+
 // The buffers of every launch rt_trace may make at the reserved geometry:
 // the most block tiles over every lanes-per-pixel shape (rt_trace picks P per
 // launch) and the current scene's mask words, so no later launch allocates.
@@ -1131,6 +1190,7 @@ static int apply_reserve(rt_device *d) {
     if (d->scene_set)
         for (int rs = 0; rs < 2; ++rs) n_words = std::max(n_words, rtk_mask_words(d->n_groups[rs]));
     if (const int rc = ensure_tile_buffers(d, n_tiles, nullptr, true)) return rc;
+    if (const int rc = ensure_sel(d, d->reserve_sel_words, nullptr, true)) return rc;  // (rt_trace_tiles)
     if (d->pixel_sort_env)
         if (const int rc = ensure_pixel_sort(d, n_tiles, d->reserve_pixels, nullptr, true))
             return rc;
@@ -1146,12 +1206,69 @@ extern "C" int rt_device_reserve(rt_device *d, uint32_t width, uint32_t local_ro
     for (const int p : {1, 2, 4, 8, 16, 32}) n_tiles = std::max(n_tiles, rtk_tile_count(width, local_rows, p));
     d->reserve_tiles = std::max(d->reserve_tiles, n_tiles);
     d->reserve_pixels = std::max(d->reserve_pixels, (size_t)width * local_rows);
+    // (rt_trace_tiles' bitmap: one bit per reference tile of a width x local_rows image)
+    d->reserve_sel_words = std::max(d->reserve_sel_words, (size_t)(rt_tile_count(width, local_rows, nullptr) + 31u) / 32u);
     return apply_reserve(d);
 }
 
-extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, uint64_t *d_rays,
-                        void *stream) {
-    DeviceGuard device_guard;  // the caller's current device is restored on return
+extern "C" uint32_t rt_tile_count(uint32_t width, uint32_t height, uint32_t *out_tiles_x) {
+    const bool ok = width != 0 && height != 0 && width <= 65536 && height <= 65536;
+    const uint32_t tx = ok ? (width + RT_TILE_SIZE - 1u) / RT_TILE_SIZE : 0u;
+    if (out_tiles_x) *out_tiles_x = tx;
+    return ok ? tx * ((height + RT_TILE_SIZE - 1u) / RT_TILE_SIZE) : 0u;
+}
+static_assert(kRefTile == RT_TILE_SIZE, "the kernels' reference tile is the header's");
+
+// A validated rt_trace_tiles list (build_selection): the bitmap the kernels read and what the
+// host derives from the list -- the pixels it covers (the lanes-per-pixel choice) and, by clipped
+// size, how many tiles it names (the block tiles inside them, for any launch shape).
+struct TileSelection {
+    const uint32_t *bits = nullptr;  // one bit per reference tile (TraceArgs.sel's layout)
+    uint32_t n_words = 0, tiles_x = 0;
+    uint64_t pixels = 0;             // of the listed tiles, clipped to the image (main.cpp:362-368)
+    // listed tiles by clipped size: [0] 32 x 32, [1] the ragged right column (clip_w x 32),
+    // [2] the ragged bottom row (32 x clip_h), [3] the corner of both (clip_w x clip_h)
+    uint32_t n_class[4] = {0, 0, 0, 0};
+    uint32_t clip_w = RT_TILE_SIZE, clip_h = RT_TILE_SIZE;
+    // block tiles of launch shape `lpp` inside the listed tiles
+    uint32_t block_tiles(int lpp) const {
+        const uint32_t T = RT_TILE_SIZE;
+        return n_class[0] * rtk_tile_count(T, T, lpp) + n_class[1] * rtk_tile_count(clip_w, T, lpp) +
+               n_class[2] * rtk_tile_count(T, clip_h, lpp) + n_class[3] * rtk_tile_count(clip_w, clip_h, lpp);
+    }
+};
+
+// Validates a tile list against a width x height image and builds its bitmap into `bits`
+// (plain host code: no device, no allocation beyond the vector's growth).  Returns 0, or -1 for an
+// index past the image's tiles (*bad = its position in the list), -2 for an index named twice.
+static int build_selection(const uint32_t *tiles, uint32_t n_tiles, uint32_t width, uint32_t height,
+                           std::vector<uint32_t> &bits, TileSelection &sel, uint32_t *bad) {
+    uint32_t tiles_x = 0;
+    const uint32_t total = rt_tile_count(width, height, &tiles_x);
+    const uint32_t tiles_y = tiles_x ? total / tiles_x : 0u;
+    sel = TileSelection();
+    sel.tiles_x = tiles_x;
+    sel.n_words = (total + 31u) / 32u;
+    sel.clip_w = width - (tiles_x - 1u) * RT_TILE_SIZE;   // the last column's and row's clipped
+    sel.clip_h = height - (tiles_y - 1u) * RT_TILE_SIZE;  // size (32 when the image is not ragged)
+    bits.assign(sel.n_words, 0u);
+    for (uint32_t i = 0; i < n_tiles; ++i) {
+        const uint32_t t = tiles[i];
+        *bad = i;
+        if (t >= total) return -1;
+        if ((bits[t >> 5] >> (t & 31u)) & 1u) return -2;
+        bits[t >> 5] |= 1u << (t & 31u);
+        const bool right = t % tiles_x == tiles_x - 1u && sel.clip_w != RT_TILE_SIZE;
+        const bool bottom = t / tiles_x == tiles_y - 1u && sel.clip_h != RT_TILE_SIZE;
+        sel.n_class[(right ? 1u : 0u) + (bottom ? 2u : 0u)] += 1u;
+        sel.pixels += (uint64_t)(right ? sel.clip_w : RT_TILE_SIZE) * (bottom ? sel.clip_h : RT_TILE_SIZE);
+    }
+    sel.bits = bits.data();
+    return 0;
+}
+
+// What rt_trace refuses before it looks at the images (rt_trace_tiles refuses the same).
+static int check_trace_args(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, uint64_t *d_rays) {
     if (!d || !cam || !desc || !d_rays) return fail(RT_EINVAL, "rt_trace: NULL argument");
     if (!d->lut_set) return fail(RT_EINVAL, "rt_trace: rsqrt table not set (rt_set_rsqrt_table)");
     if (!d->scene_set) return fail(RT_EINVAL, "rt_trace: no scene uploaded (rt_scene_upload)");
@@ -1166,6 +1283,17 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     if (band_rows % 8u) return fail(RT_EINVAL, "rt_trace: BandRows must be a multiple of 8");
     if ((uint64_t)desc->PreviousRayCount + desc->Frames > 0xFFFFFFFFull)
         return fail(RT_EINVAL, "rt_trace: PreviousRayCount + Frames exceeds the u32 frame count");
+    return RT_OK;
+}
+
+// rt_trace, over every tile of the band (sel == NULL) or over the listed reference tiles of the
+// full image (rt_trace_tiles: one band, sel validated against desc's image and not empty).
+static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const TileSelection *sel,
+                        uint64_t *d_rays, void *stream) {
+    DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (const int rc = check_trace_args(d, cam, desc, d_rays)) return rc;
+    const uint32_t band_rows = desc->BandRows ? desc->BandRows : 32u;
+    const uint32_t band_count = desc->BandCount ? desc->BandCount : 1u;
     const uint32_t local_rows = rt_band_local_rows(desc->Height, band_rows, band_count, desc->BandIndex);
     if (desc->Frames == 0 || local_rows == 0) return RT_OK;
     if (!cam->CurrentImage.Data || !cam->PreviousImage.Data)
@@ -1249,7 +1377,8 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     int lpp = d->lanes_per_pixel;
     const bool auto_lpp = lpp == 0;
     if (lpp == 0) {
-        const uint64_t pixels = (uint64_t)desc->Width * local_rows;
+        // (a tile list: the pixels it covers -- a small window is a small launch, like a small rank share)
+        const uint64_t pixels = sel ? sel->pixels : (uint64_t)desc->Width * local_rows;
         lpp = pixels >= (uint64_t)d->cu_count * 6144u ? 4 : pixels >= (uint64_t)d->cu_count * 3072u ? 8 : 16;
         while (lpp > 1 && (uint32_t)lpp / 2u >= desc->Frames) lpp /= 2;
     }
@@ -1323,6 +1452,12 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
         memcpy(&u, &f, 4);
         key.push_back(u);
     }
+    // the selection is part of the key, word for word (never a hash: a collision would reuse another
+    // list's masks and order); 64 words at 1080p, 131,072 at the 65536^2 limit
+    key.push_back(sel ? 1u : 0u);
+    if (sel) key.insert(key.end(), sel->bits, sel->bits + sel->n_words);
+    // block tiles inside the listed tiles (every tile's without a list)
+    const uint32_t n_selected = sel ? sel->block_tiles(lpp) : n_tiles;
     if (!d->tile_stream_set || s != d->tile_stream) {
         // order, masks and costs are written and read in stream order: on a new
         // stream, every launch issued on the previous one must have finished (the
@@ -1341,12 +1476,21 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     const bool pixel_sort = d->pixel_sort_env && sched && lpp >= 4 && !a.interleave;
     if (pixel_sort)
         if (const int rc = ensure_pixel_sort(d, n_tiles, (size_t)desc->Width * local_rows, s, false)) return rc;
+    if (sel)
+        if (const int rc = ensure_sel(d, sel->n_words, s, false)) return rc;
     const bool new_key = key != d->tile_key;
+    // the key's bitmap on the device (uploaded below when the key is new; the same list again finds it there)
+    a.sel = sel ? d->d_sel : nullptr;
+    a.sel_tiles_x = sel ? sel->tiles_x : 0u;
     // (the table is written by the key's cull pass: the key holds the camera and the scene)
     a.prim = cull ? d->d_prim[rs] : nullptr;
     uint32_t head_frames = 0;  // > 0: split this launch (first launch of a key, below): frames of the leading parts
     uint32_t split[8], n_split = 0;
     if (new_key) {
+        // (first, so that a failed upload leaves no key behind that claims its bitmap is on the device)
+        d->tile_key.clear();
+        if (sel)
+            if (const int rc = sel_upload(d, sel->bits, sel->n_words, s)) return rc;
         d->tile_key = key;
         d->n_sorts = 0;
         if (pixel_sort) HIP_OK(hipMemsetAsync(d->d_pix_perm, 0xFF, (size_t)n_tiles * 64u, s));  // identity
@@ -1389,11 +1533,20 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
             // no cull pass: every block tile is live, and the totals word the XCD grouping reads
             // (rtk_launch_xcd_group) says so (u64 little-endian: low word n_tiles, the rest 0)
             HIP_OK(hipMemsetAsync(d->d_cull_counters + kCullTotals, 0, 2 * sizeof(unsigned long long), s));
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(d->d_cull_counters + kCullTotals), n_tiles, 1, s));
-            d->n_live = n_tiles;
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(d->d_cull_counters + kCullTotals), n_selected, 1, s));
+            d->n_live = n_selected;
             d->dead_pixels = 0;
             d->counts_known = true;
             d->tile_order_valid = false;  // identity until a measured sort exists
+            if (sel) {
+                // a tile list: the identity order would trace unlisted tiles, so the selected
+                // tiles (cost 2, the others 0) are sorted to the front and the grid is their count
+                if (rtk_launch_select(&a, lpp, d->d_tile_live, d->d_tile_cost, s) != 0 ||
+                    rtk_launch_tile_sort(d->d_tile_cost, d->d_tile_order, d->d_tile_scratch, n_units, s) != 0)
+                    return fail(RT_EIO, "rt_trace_tiles: select pass launch failed: %s",
+                                hipGetErrorString(hipGetLastError()));
+                d->tile_order_valid = true;
+            }
         }
     }
     // live-tile count: on the host once the cull totals have landed, else read
@@ -1402,16 +1555,19 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     const uint32_t grid_tiles = known ? d->n_live : n_tiles;
     a.live_total = known ? nullptr : d->d_cull_counters + kCullTotals;
     const bool any_live = !known || d->n_live > 0;
-    const bool any_dead = empty_capable && (!known || d->n_live < n_tiles);
+    const bool any_dead = empty_capable && (!known || d->n_live < n_selected);
     a.masks = cull ? d->d_masks : nullptr;
     a.tile_order = d->tile_order_valid ? d->d_tile_order : nullptr;
+    // (the identity order knows no selection: both paths above leave a sorted order for a tile list)
+    if (sel && !a.tile_order) return fail(RT_EIO, "rt_trace_tiles: no tile order for the selection");
     a.tile_cost = sched ? d->d_tile_cost : nullptr;
     a.pix_perm = pixel_sort ? d->d_pix_perm : nullptr;
     a.pix_seg = d->pixel_seg;
     // (multi-frame launches only: a one-frame launch, OnRender's, keeps its store and one kernel fewer)
     a.skip_cur = d->cur_pass && lpp >= 2 ? 1u : 0u;
     d->last.PixelsSorted = pixel_sort && !new_key && d->n_sorts > 0 ? 1u : 0u;
-    d->last_n_tiles = n_tiles;
+    d->last_n_tiles = n_selected;  // (SegmentsFolded: the dead tiles among these)
+    d->last.TilesSelected = n_selected;
     d->last_frames = desc->Frames;
     d->last_empty_capable = empty_capable;
     d->last.LanesPerPixel = lanes;
@@ -1466,11 +1622,38 @@ extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_
     }
     // options EncodePass: the RGBA8 band image from the running mean the kernels stored (main.cpp:490's
     // store on its own, the same bits), written by one coalesced pass
+    // (a tile list: over the listed tiles' pixels only, so no other RGBA8 pixel is written)
     if (a.skip_cur && desc->Frames > 0 &&
-        rtk_launch_encode(a.prev, a.cur, (uint64_t)local_rows * desc->Width, (a.flags & kFlagSrgbPow) ? 1u : 0u, s) != 0)
+        (sel ? rtk_launch_encode_selected(&a, s)
+             : rtk_launch_encode(a.prev, a.cur, (uint64_t)local_rows * desc->Width, (a.flags & kFlagSrgbPow) ? 1u : 0u,
+                                 s)) != 0)
         return fail(RT_EIO, "rt_trace: RGBA8 encode launch failed: %s", hipGetErrorString(hipGetLastError()));
     d->last.SplitHeadFrames = head_frames;
     return RT_OK;
+}
+
+extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, uint64_t *d_rays,
+                        void *stream) {
+    return trace_launch(d, cam, desc, nullptr, d_rays, stream);
+}
+
+extern "C" int rt_trace_tiles(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const uint32_t *tiles,
+                              uint32_t n_tiles, uint64_t *d_rays, void *stream) {
+    if (const int rc = check_trace_args(d, cam, desc, d_rays)) return rc;
+    if (desc->BandCount > 1u || desc->BandIndex != 0u)
+        return fail(RT_EINVAL, "rt_trace_tiles: tiles index the whole image (BandCount 0 or 1, BandIndex 0)");
+    if (!tiles && n_tiles) return fail(RT_EINVAL, "rt_trace_tiles: tiles is NULL with n_tiles %u", n_tiles);
+    // the list is consumed here: the bitmap lives in the device's own host vector, and a new key's
+    // upload goes through the library's pinned slots, so the caller's array is free on return
+    TileSelection sel;
+    uint32_t bad = 0;
+    const int v = build_selection(tiles, n_tiles, desc->Width, desc->Height, d->sel_bits, sel, &bad);
+    if (v == -1)
+        return fail(RT_EINVAL, "rt_trace_tiles: tiles[%u] = %u, the image has %u tiles", bad, tiles[bad],
+                    rt_tile_count(desc->Width, desc->Height, nullptr));
+    if (v == -2) return fail(RT_EINVAL, "rt_trace_tiles: tiles[%u] = %u is listed twice", bad, tiles[bad]);
+    if (n_tiles == 0 || desc->Frames == 0) return RT_OK;
+    return trace_launch(d, cam, desc, &sel, d_rays, stream);
 }
 
 extern "C" int rt_assemble_bands(const void *d_compact, uint64_t rank_stride_bytes, void *d_dst, uint32_t width,

@@ -119,7 +119,19 @@ struct TraceArgs {
     // one table per device computed once (rt_device_create): a finished sample's two weights are one
     // gather instead of two conversions, a reciprocal and a division (one-wave kernels)
     const float2 *weights;
+    // optional (rt_trace_tiles): the launch covers only the listed reference tiles (kRefTile x kRefTile
+    // pixels, main.cpp:9).  One bit per reference tile, bit t & 31 of word t >> 5 with
+    // t = TileY * sel_tiles_x + TileX; NULL = every tile.  Read by the scheduling kernels only
+    // (rt_sched.hip: cull / select, pixel sort, encode): every launch shape's block tile divides a
+    // reference tile (rtk_shape.h), so a selection is a set of whole block tiles and the trace
+    // kernels see nothing but a shorter live prefix of tile_order.
+    const uint32_t *sel;
+    uint32_t sel_tiles_x;        // reference tiles per image row: ceil(width / kRefTile)
 };
+constexpr uint32_t kRefTile = 32;  // the reference's TileSize (main.cpp:9; RT_TILE_SIZE of rt_trace.h)
+// live[] values of a block tile (rtk_launch_cull / rtk_launch_select): dead (folded by rtk_launch_empty),
+// live (traced), or outside the launch's tile selection (neither: no byte of it is written)
+enum { kTileDead = 0, kTileLive = 1, kTileSkipped = 2 };
 constexpr uint32_t kWeightsN = 65536;
 constexpr uint32_t kPrimF4 = 4;
 constexpr uint32_t kMergeGroups = 2;
@@ -235,9 +247,21 @@ extern "C" int rtk_launch_trace_grid(const TraceArgs *a, int simd, int src, int 
 // first); counters[0, 64) sum to the live tiles, counters[64, 128) to the
 // image pixels of dead tiles (zeroed by the call), and counters[kCullTotals],
 // counters[kCullTotals + 1] receive the two sums (kCullCounterWords words).
+// With a selection (a->sel) a block tile outside it leaves before any of that:
+// live[t] = kTileSkipped, cost 0, no mask words written and nothing counted --
+// whether or not the launch is empty_capable -- so the totals are those of the
+// selected tiles and the sorted order's prefix holds selected live tiles only.
 extern "C" int rtk_launch_cull(const TraceArgs *a, int lanes_per_pixel, uint32_t *live, uint32_t *cost,
                                unsigned long long *counters, int empty_capable, hipStream_t stream);
-// Pixels of dead block tiles (live[t] == 0): every sample misses with no sky,
+// The cull pass's stand-in for a selection on a device without culling (a->sel set):
+// live[t] = kTileLive / kTileSkipped and cost 2 / 0 per unit from the bitmap, so that a tile
+// sort puts the selected tiles first (the caller sets the totals: it knows the count).
+extern "C" int rtk_launch_select(const TraceArgs *a, int lanes_per_pixel, uint32_t *live, uint32_t *cost,
+                                 hipStream_t stream);
+// rtk_launch_encode over the pixels of the selected reference tiles of a full image
+// (a->prev -> a->cur, a->width x a->local_rows, a->sel set): no other RGBA8 pixel is written.
+extern "C" int rtk_launch_encode_selected(const TraceArgs *a, hipStream_t stream);
+// Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:
 // the cull pass's device total, so the host need not read it back).

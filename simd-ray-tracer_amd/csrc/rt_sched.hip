@@ -1,7 +1,8 @@
 // rt_sched.hip — the kernels around the trace launch: the primary-ray cull
 // pass, dead-tile fold, primary group rows, pixel sort, heaviest-first tile
 // sort, XCD grouping, RGBA8 encode, ray-counter sum and band assembly, with
-// their launchers and the tile geometry queries.
+// their launchers and the tile geometry queries.  A launch over a list of
+// reference tiles (rt_trace_tiles, TraceArgs.sel) is decided here alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -112,6 +113,16 @@ __device__ __forceinline__ uint64_t wave_tile_mask(const TraceArgs &a, const Con
 // block tiles, [64, 128) image pixels of dead block tiles.
 constexpr uint32_t kCullStripes = 64;
 
+// Tile selection (TraceArgs.sel, rt_trace_tiles): whether block tile (tile_x, tile_y) of launch
+// shape P lies in a listed reference tile.  Block tiles divide the reference tile (rtk_shape.h),
+// so its first pixel decides; that pixel is inside the image, so the bit exists.
+template <int P>
+__device__ __forceinline__ bool tile_selected(const TraceArgs &a, uint32_t tile_x, uint32_t tile_y) {
+    if (!a.sel) return true;
+    const uint32_t t = ((tile_y * 2u * Shape<P>::TH) / kRefTile) * a.sel_tiles_x + (tile_x * 2u * Shape<P>::TW) / kRefTile;
+    return ((a.sel[t >> 5] >> (t & 31u)) & 1u) != 0u;
+}
+
 // The cull pass: one block per block tile, one wave per wave tile (the trace
 // kernel's geometry).  Runs once per camera / scene / launch geometry; the
 // trace launches reuse its masks and live-tile list.
@@ -122,6 +133,20 @@ __global__ __launch_bounds__(256) void cull_kernel(TraceArgs a, uint32_t *live, 
     __shared__ uint32_t s_any;
     const uint32_t tile = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
+    // A block tile outside the launch's selection is neither live nor dead: not traced, not
+    // folded, not counted, its mask words not written (block-uniform, before the barrier).
+    // This holds for launches that fold nothing too (!empty_capable), where every other tile is live.
+    if (!tile_selected<P>(a, tile_x, tile_y)) {
+        if (threadIdx.x == 0) {
+            live[tile] = kTileSkipped;
+            if (a.unit_waves) {
+                for (uint32_t w = 0; w < 4u; ++w) cost[4u * tile + w] = 0u;
+            } else {
+                cost[tile] = 0u;
+            }
+        }
+        return;
+    }
     // the wave tile's pixel extent [x0, x1] x [ly0, ly1] (see trace_kernel)
     const uint32_t x0 = tile_x * (2u * TW) + (a.interleave ? (wave & 1u) : (wave & 1u) * TW);
     const uint32_t ly0 = tile_y * (2u * TH) + (a.interleave ? (wave >> 1) : (wave >> 1) * TH);
@@ -180,6 +205,22 @@ __global__ __launch_bounds__(64) void cull_total_kernel(unsigned long long *coun
     }
 }
 
+// The selection on a device without a cull pass (rt_device_options Cull off): one thread per
+// block tile writes what cull_kernel would for a scene it cannot cull -- selected tiles live
+// with cost 2, the others skipped with cost 0 -- so the tile sort that follows puts the
+// selected tiles first and the trace grid is their count.
+template <int P>
+__global__ __launch_bounds__(256) void select_kernel(TraceArgs a, uint32_t n_tiles, uint32_t *live, uint32_t *cost) {
+    const uint32_t tile = blockIdx.x * 256u + threadIdx.x;
+    if (tile >= n_tiles) return;
+    const bool l = tile_selected<P>(a, tile % a.tiles_x, tile / a.tiles_x);
+    live[tile] = l ? kTileLive : kTileSkipped;
+    if (a.unit_waves) {
+        for (uint32_t w = 0; w < 4u; ++w) cost[4u * tile + w] = l ? 2u : 0u;
+    } else {
+        cost[tile] = l ? 2u : 0u;
+    }
+}
 
 // Pixels of dead block tiles: no sphere group passes any of the tile's
 // (conservative) cone tests, so every primary ray of every sample misses;
@@ -206,7 +247,8 @@ __global__ __launch_bounds__(256) void empty_kernel(TraceArgs a, const uint32_t 
         if (dead_rays) atomicAdd(a.rays, dead_rays);
     }
     const uint32_t x = blockIdx.x * 256u + threadIdx.x, ly = blockIdx.y;
-    if (!(x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == 0u)) return;
+    // (dead tiles only: a tile outside the launch's selection is kTileSkipped and keeps every byte)
+    if (!(x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == kTileDead)) return;
     const size_t pix = (size_t)ly * a.width + x;
     float accx = 0.0f, accy = 0.0f, accz = 0.0f;
     if (fold) {
@@ -244,6 +286,9 @@ __global__ __launch_bounds__(64) void pixel_sort_kernel(TraceArgs a, uint8_t *pe
     const uint32_t tile = blockIdx.x, lane = threadIdx.x;
     const uint32_t tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
     uint8_t *pp = perm + (size_t)tile * 64u;
+    // a block tile outside the launch's selection is never traced: its masks and costs were never
+    // written, and its entry stays "not permuted" (the key's first launch marked every tile so)
+    if (!tile_selected<P>(a, tile_x, tile_y)) return;
     // a quadrant without candidate groups folds without tracing: keep such blocks as they are
     if (a.masks) {
         const uint32_t n_words = rtk_mask_words(a.n_groups);
@@ -658,6 +703,19 @@ extern "C" int rtk_launch_cull(const TraceArgs *a, int lanes_per_pixel, uint32_t
 }
 
 template <int P>
+static void launch_select_p(const TraceArgs *a, uint32_t *live, uint32_t *cost, hipStream_t stream) {
+    const uint32_t n = rtk_tile_count(a->width, a->local_rows, P);
+    hipLaunchKernelGGL(rtk::select_kernel<P>, dim3((n + 255u) / 256u), dim3(256), 0, stream, *a, n, live, cost);
+}
+
+extern "C" int rtk_launch_select(const TraceArgs *a, int lanes_per_pixel, uint32_t *live, uint32_t *cost,
+                                 hipStream_t stream) {
+    if (!a->sel) return -1;
+    RTK_BY_P(launch_select_p, a, live, cost, stream)
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+template <int P>
 static void launch_empty_p(const TraceArgs *a, const uint32_t *live, const unsigned long long *dead_pixels,
                            hipStream_t stream) {
     hipLaunchKernelGGL(rtk::empty_kernel<P>, dim3((a->width + 255u) / 256u, a->local_rows), dim3(256), 0, stream, *a,
@@ -704,6 +762,29 @@ extern "C" int rtk_launch_encode(const void *accum, void *out, uint64_t n, uint3
     const uint32_t grid = (uint32_t)(blocks < 8192u ? blocks : 8192u);
     hipLaunchKernelGGL(rtk::encode_kernel, dim3(grid), dim3(256), 0, stream, (const float4 *)accum, (uint32_t *)out, n,
                        pow_mode);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+namespace rtk {
+// encode_kernel over the listed reference tiles of a full image (rt_trace_tiles with the encode
+// pass): one thread per pixel of a row; a pixel of an unlisted tile is neither read nor written.
+__global__ __launch_bounds__(256) void encode_selected_kernel(const float4 *accum, uint32_t *out, uint32_t width,
+                                                              const uint32_t *sel, uint32_t sel_tiles_x, uint32_t pw) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
+    if (x >= width) return;
+    const uint32_t t = (y / kRefTile) * sel_tiles_x + x / kRefTile;
+    if (!((sel[t >> 5] >> (t & 31u)) & 1u)) return;
+    const size_t i = (size_t)y * width + x;
+    const float4 v = accum[i];
+    out[i] = rgba8(v.x, v.y, v.z, pw != 0u);
+}
+}  // namespace rtk
+
+extern "C" int rtk_launch_encode_selected(const TraceArgs *a, hipStream_t stream) {
+    if (!a->sel || a->width == 0 || a->local_rows == 0) return -1;
+    hipLaunchKernelGGL(rtk::encode_selected_kernel, dim3((a->width + 255u) / 256u, a->local_rows), dim3(256), 0, stream,
+                       (const float4 *)a->prev, a->cur, a->width, a->sel, a->sel_tiles_x,
+                       (a->flags & kFlagSrgbPow) ? 1u : 0u);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -55,6 +55,9 @@ struct Shape {
     static constexpr uint32_t TW = P == 0 ? 16u : P <= 2 ? 8u : P <= 8 ? 4u : 2u;
     static constexpr uint32_t TH = P == 0 ? 16u : P == 1 ? 8u : P <= 4 ? 4u : P <= 16 ? 2u : 1u;
     static_assert(TW * TH * LP == 64u * Q, "a wave is 64 lanes");
+    // a block tile (2TW x 2TH) lies in exactly one reference tile, so a tile selection
+    // (TraceArgs.sel) is a set of whole block tiles
+    static_assert(kRefTile % (2u * TW) == 0 && kRefTile % (2u * TH) == 0, "block tiles divide the reference tile");
 };
 
 // Occupancy target of the one-wave kernels per secondary walk: the two-word
