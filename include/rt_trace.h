@@ -293,7 +293,8 @@ uint32_t rt_tile_count(uint32_t width, uint32_t height, uint32_t *out_tiles_x);
  *    counted analytically (dead tiles).  A list naming every tile gives rt_trace's bits and count.
  *  - PreviousRayCount is per call, as for rt_trace: frame k's seeds and weights depend on
  *    PreviousRayCount + k only, so a caller whose tiles carry different sample counts keeps one
- *    count per tile and lists together the tiles that share one.
+ *    count per tile and lists together the tiles that share one (or hands every tile's own
+ *    count to rt_trace_tile_work, below, in one call).
  *  - RT_EINVAL, before anything is enqueued: tiles == NULL with n_tiles > 0, an index >=
  *    rt_tile_count(Width, Height), an index named twice (the reference's queue would fold that
  *    tile twice; the library refuses rather than guess), and everything rt_trace refuses.
@@ -312,6 +313,54 @@ uint32_t rt_tile_count(uint32_t width, uint32_t height, uint32_t *out_tiles_x);
  *    lists earlier) if that copy has not finished yet. */
 int rt_trace_tiles(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
                    const uint32_t *tiles, uint32_t n_tiles, uint64_t *d_rays, void *stream);
+
+/* one entry of a caller's tile queue: the reference's WorkEntry plus the tile's own counts */
+typedef struct rt_tile_work {
+    uint32_t Tile;             /* TileY*TilesX + TileX, as rt_trace_tiles                     */
+    uint32_t PreviousRayCount; /* frames already folded into this tile's pixels               */
+    uint32_t Frames;           /* frames to fold into them now; 0: the entry is dropped       */
+} rt_tile_work;
+
+/* rt_trace_tiles with a (PreviousRayCount, Frames) pair per tile, in one launch: the dispatch of an
+ * adaptive or progressive sampler whose tiles sit at different sample counts.  Nothing in RenderTile
+ * couples a tile's frame count to another's (main.cpp:362-368, 484-487); the host keeps one count per
+ * tile.  work: HOST array of n_work entries, any order.  rt_trace_tiles' contract holds, except:
+ *  - Every pixel of an entry's tile receives exactly the running mean and RGBA8 that rt_trace writes
+ *    for it when desc->PreviousRayCount / Frames are replaced by the entry's values.  No byte of any
+ *    other pixel of either image is written, the tiles of entries with Frames == 0 included.
+ *    desc->PreviousRayCount and desc->Frames are not read.
+ *  - *d_rays grows by the listed tiles' segments, each tile contributing its own frames, traced or
+ *    counted analytically (dead tiles).
+ *  - RT_FLAG_ACCUM_ZERO and RT_FLAG_SRGB_POW apply to the whole call; an entry with
+ *    PreviousRayCount == 0 does not read its pixels' mean, as rt_trace does not.
+ *  - RT_EINVAL, before anything is enqueued or any key state changes: what rt_trace_tiles refuses
+ *    (work == NULL with n_work > 0, an index out of range, an index listed twice, bands), and an
+ *    entry whose PreviousRayCount + Frames does not fit a u32.  A tile listed twice is refused even
+ *    when one of its entries has Frames == 0: duplicates are refused before such entries are dropped.
+ *    n_work == 0, or every entry at Frames == 0: RT_OK, nothing enqueued.
+ *  - The counts are no part of the launch key.  The key holds the list of tiles with Frames > 0
+ *    (compared by content) and nothing of their counts: the same tiles with other counts reuse the
+ *    cull masks, the tile order and the pixel permutation (CullPassRan 0), and the key is the same
+ *    whether the list came from rt_trace_tiles or from here.
+ *  - The per-tile table (two words per tile of the image) is uploaded on every call with mixed counts,
+ *    from one of two pinned staging slots the library owns, like a new list's bitmap; the host array
+ *    is consumed before the call returns.  The call may wait where rt_trace_tiles may wait and for a
+ *    table slot's previous upload (two such calls earlier), nothing else.  rt_device_reserve also
+ *    sizes the table and its staging.
+ *  - When every kept entry has the same pair, the call IS rt_trace_tiles with that pair: the same
+ *    path and kernels, the first-launch split and the 4-pixels-per-lane shape at Frames == 1 included
+ *    (rt_trace_last_tile_counts 0).
+ *  - Mixed counts (rt_trace_last_tile_counts 1): the first-launch split does not apply (SplitHeadFrames 0; a
+ *    per-tile split is not built).  With LanesPerPixel at its default the lanes follow the listed
+ *    pixel count per CU, as for rt_trace_tiles, and never exceed the LARGEST Frames of the list; at
+ *    a largest Frames of 1 the launch takes the 4-pixels-per-lane shape.  The trace kernels are the
+ *    launch's usual ones compiled to take each block tile's pair from the table; the four-wave
+ *    kernels (OneWaveGroups off) exist so for a scene in the LDS image read through the scalar cache
+ *    only -- with SphereSourceLds or SceneInHbm on, or a scene beyond the LDS image, a mixed launch of
+ *    such a device runs the one-wave run-time kernel (OneWaveGroups 1, Walk 0 in rt_trace_info; the
+ *    wave-ranked order makes it another key than the device's uniform launches of that list). */
+int rt_trace_tile_work(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
+                       const rt_tile_work *work, uint32_t n_work, uint64_t *d_rays, void *stream);
 
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
@@ -368,6 +417,12 @@ typedef struct rt_trace_info {
                                  dead selected tiles' segments only             */
 } rt_trace_info;
 int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
+/* *out = 1 when the last launch on `dev` took per-tile counts (rt_trace_tile_work with mixed pairs),
+ * 0 otherwise (rt_trace, rt_trace_tiles, a work list of one pair).  A query of its own: rt_trace_info keeps
+ * the layout and the last field its callers know.  Host-side bookkeeping, never waits.  After such a
+ * launch rt_trace_last_info's SegmentsFolded is summed on the device -- each dead block tile's in-image
+ * pixels times its own tile's frames -- and that call waits for the sum as it does for the cull totals. */
+int rt_trace_last_tile_counts(rt_device *dev, uint32_t *out);
 
 /* Pre-sizes the device's launch buffers (tile order / cost / live lists, the
  * cull pass's masks and counters) for bands of up to `width` x `local_rows`
@@ -379,7 +434,8 @@ int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
  * rt_scene_upload re-applies the reservation for a larger one (if that fails,
  * the upload still succeeds and the reservation is dropped: later launches
  * grow their buffers as they need).  Also sizes what rt_trace_tiles needs for
- * a width x local_rows image (the selection bitmap and its pinned staging).
+ * a width x local_rows image (the selection bitmap and its pinned staging) and
+ * what rt_trace_tile_work needs beyond that (the per-tile table and its staging).
  * Waits for the device.  (New; the reference's arena is sized once in OnInit,
  * main.cpp:658.) */
 int rt_device_reserve(rt_device *dev, uint32_t width, uint32_t local_rows);

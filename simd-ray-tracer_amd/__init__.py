@@ -95,6 +95,10 @@ class RtTraceInfo(ctypes.Structure):  # rt_trace_last_info
         "TilesSelected")]
 
 
+class RtTileWork(ctypes.Structure):  # rt_tile_work: one entry of rt_trace_tile_work's queue
+    _fields_ = [("Tile", c_uint32), ("PreviousRayCount", c_uint32), ("Frames", c_uint32)]
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -172,9 +176,12 @@ SIGNATURES = {
     "rt_tile_count": (c_uint32, [c_uint32, c_uint32, POINTER(c_uint32)]),
     "rt_trace_tiles": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32, c_void_p,
                                c_void_p]),
+    "rt_trace_tile_work": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
+                                   c_void_p, c_void_p]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
+    "rt_trace_last_tile_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
     "rt_encode_rgba8": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p]),
     "rt_device_synchronize": (c_int, [c_void_p]),
     "rt_multi_create": (c_int, [POINTER(c_int), c_uint32, c_uint32, POINTER(c_void_p)]),
@@ -349,6 +356,20 @@ def tiles_of_rect(width: int, height: int, x0: int, y0: int, x1: int, y1: int) -
             for tx in range(x0 // RT_TILE_SIZE, (x1 - 1) // RT_TILE_SIZE + 1)]
 
 
+def tile_work_array(work) -> np.ndarray:
+    """(n, 3) uint32 array of rt_tile_work records {Tile, PreviousRayCount, Frames} from a sequence
+    of (tile, prev_count, frames) triples or an (n, 3) integer array; ValueError for anything else
+    (another shape, non-integers, values outside u32).  Pure Python (no library call)."""
+    w = np.asarray(list(work) if not isinstance(work, np.ndarray) else work)
+    if w.size == 0:
+        return np.zeros((0, 3), np.uint32)
+    if w.ndim != 2 or w.shape[1] != 3 or w.dtype.kind not in "iu":
+        raise ValueError("work: (tile, prev_count, frames) triples of integers, or an (n, 3) integer array")
+    if int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF:
+        raise ValueError("work: tile indices and counts are u32 values")
+    return np.ascontiguousarray(w.astype(np.uint32))
+
+
 def scene_prefilter(scene: RtScene, simd: bool = True):
     """(r2, r2p, flags) per sphere slot 4*group+lane as rt_scene_upload packs
     them: the exact test's r^2, the secondary-ray prefilter threshold, and
@@ -479,13 +500,39 @@ class Device:
                                     c_void_p(t.ctypes.data if t.size else None), int(t.size), c_void_p(rays_ptr),
                                     c_void_p(stream or 0)), "rt_trace_tiles")
 
+    def trace_tile_work(self, cam: RtCameraInfo, *, work, width: int, height: int, prev_ptr: int, cur_ptr: int,
+                        rays_ptr: int, max_bounce: int = 5, simd: bool = True, band_rows: int = 32,
+                        accum_zero: bool = False, srgb_pow: bool = False, stream: Optional[int] = None) -> None:
+        """trace_tiles() with each tile's own counts in one launch (rt_trace_tile_work): `work` is a
+        sequence of (tile, prev_count, frames) triples or an (n, 3) integer array; every listed tile
+        folds `frames` frames from its own `prev_count`, an entry with frames == 0 is dropped, and no
+        pixel outside the listed tiles is written.  The counts are no part of the launch key: the same
+        tiles with other counts reuse the cull masks and the learned order.  The array is consumed
+        before the call returns."""
+        w = tile_work_array(work)
+        c = RtCameraInfo()
+        ctypes.pointer(c)[0] = cam
+        c.CurrentImage = RtImage(cur_ptr, width, height, RT_FORMAT_R8G8B8A8_U32)
+        c.PreviousImage = RtImage(prev_ptr, width, height, RT_FORMAT_R32B32G32A32_F32)
+        d = RtTraceDesc(width, height, 0, 0, max_bounce, 1 if simd else 0, RT_SEED_PIXEL, band_rows, 1, 0,
+                        (RT_FLAG_ACCUM_ZERO if accum_zero else 0) | (RT_FLAG_SRGB_POW if srgb_pow else 0))
+        _check(lib().rt_trace_tile_work(self.handle, ctypes.byref(c), ctypes.byref(d),
+                                        c_void_p(w.ctypes.data if w.size else None), int(w.shape[0]),
+                                        c_void_p(rays_ptr), c_void_p(stream or 0)), "rt_trace_tile_work")
+
     def last_info(self) -> dict:
         """What the last trace launched (rt_trace_last_info): segments counted
         but folded analytically (dead tiles), P, tiles traced / total, whether
-        the cull pass ran."""
+        the cull pass ran; plus "TileCounts" (rt_trace_last_tile_counts): 1 when the launch took
+        per-tile counts."""
         info = RtTraceInfo()
         _check(lib().rt_trace_last_info(self.handle, ctypes.byref(info)), "rt_trace_last_info")
-        return {n: int(getattr(info, n)) for n, _ in RtTraceInfo._fields_}
+        out = {n: int(getattr(info, n)) for n, _ in RtTraceInfo._fields_}
+        tc = c_uint32(0)
+        if hasattr(lib(), "rt_trace_last_tile_counts"):  # (an older A/B build, RT_TRACE_LIB, has no such launches)
+            _check(lib().rt_trace_last_tile_counts(self.handle, ctypes.byref(tc)), "rt_trace_last_tile_counts")
+        out["TileCounts"] = int(tc.value)
+        return out
 
     def reserve(self, width: int, local_rows: int) -> None:
         """rt_device_reserve: pre-size the launch buffers for bands up to width x local_rows."""

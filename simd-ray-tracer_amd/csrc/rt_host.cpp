@@ -13,6 +13,17 @@
 #include "rt_kernel.h"
 #include "rt_trace.h"
 
+// Two pinned slots the library owns, from which words a launch reads on the device are uploaded.
+// Each slot is guarded by an event recorded after its copy and is rewritten only once that copy has
+// finished (staged_upload), so the caller's array is free when the call returns and back-to-back
+// calls do not wait for each other.
+struct StagedWords {
+    uint32_t *h[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool in_flight[2] = {false, false};
+    uint32_t slot = 0;
+};
+
 struct rt_device {
     int ordinal = 0;
     hipStream_t stream = nullptr;
@@ -121,15 +132,23 @@ struct rt_device {
     // rt_trace_tiles: the selection bitmap of the current tile key on the device (TraceArgs.sel; its
     // words are part of tile_key, so keys compare by the lists' content).  A new key's bitmap is
     // uploaded from one of two pinned slots, each guarded by an event recorded after its copy: a
-    // slot is rewritten only once that copy has finished (sel_upload)
+    // slot is rewritten only once that copy has finished (staged_upload).
+    // rt_trace_tile_work: the per-tile {PreviousRayCount, Frames} table of a launch with mixed counts
+    // (TraceArgs.tile_counts_at: two words per reference tile of the image) lies behind the bitmap in
+    // d_sel (rt_kernel.h rtk_sel_table_at) and is uploaded on EVERY such call -- the counts are no part
+    // of the key -- through two pinned slots of its own, by the same scheme
     uint32_t *d_sel = nullptr;
-    uint32_t *h_sel[2] = {nullptr, nullptr};
-    hipEvent_t ev_sel[2] = {nullptr, nullptr};
-    bool sel_in_flight[2] = {false, false};
-    uint32_t sel_slot = 0;
-    size_t sel_cap = 0;              // words of d_sel and of each pinned slot
-    size_t reserve_sel_words = 0;    // rt_device_reserve: the most bitmap words of any geometry reserved
+    StagedWords sel, counts;
+    uint32_t sel_cap = 0;            // reference tiles d_sel and the pinned slots are sized for
+    uint32_t reserve_ref_tiles = 0;  // rt_device_reserve: the most reference tiles of any geometry reserved
     std::vector<uint32_t> sel_bits;  // rt_trace_tiles builds the call's bitmap here (no allocation per call)
+    std::vector<uint32_t> work_tiles, counts_table;  // the call's tile list and table (no allocation per call)
+    // such a launch's folded segments are summed on the device (d_cull_counters[kCullFolded]) and
+    // follow to the host like the cull totals: pinned h_folded, event ev_folded
+    unsigned long long *h_folded = nullptr;
+    hipEvent_t ev_folded = nullptr;
+    bool last_folded_on_device = false;  // the last launch's SegmentsFolded is h_folded's (rt_trace_last_info)
+    bool last_tile_counts = false;       // the last launch took per-tile counts (rt_trace_last_tile_counts)
     uint64_t scene_gen = 0;  // bumped by every rt_scene_upload
     // the last stream rt_trace ran on (a switch waits for the device: below)
     hipStream_t tile_stream = nullptr;
@@ -260,7 +279,9 @@ extern "C" int rt_device_create_ex(int hip_device, const rt_device_options *opti
         hipMalloc(&d->d_lut, 2048 * sizeof(float)) != hipSuccess ||
         hipMalloc(&d->d_weights, kWeightsN * sizeof(float2)) != hipSuccess ||
         hipHostMalloc(&d->h_counts, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&d->ev_counts, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&d->ev_counts, hipEventDisableTiming) != hipSuccess ||
+        hipHostMalloc(&d->h_folded, sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&d->ev_folded, hipEventDisableTiming) != hipSuccess) {
         rt_device_destroy(d);
         return fail(RT_ENOMEM, "rt_device_create: stream/LUT/event allocation failed");
     }
@@ -324,10 +345,14 @@ extern "C" int rt_device_destroy(rt_device *d) {
     (void)hipFree(d->d_pix_perm);
     (void)hipFree(d->d_pix_cost);
     (void)hipFree(d->d_sel);
-    for (int i = 0; i < 2; ++i) {
-        if (d->h_sel[i]) (void)hipHostFree(d->h_sel[i]);
-        if (d->ev_sel[i]) (void)hipEventDestroy(d->ev_sel[i]);
+    for (StagedWords *w : {&d->sel, &d->counts}) {
+        for (int i = 0; i < 2; ++i) {
+            if (w->h[i]) (void)hipHostFree(w->h[i]);
+            if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
+        }
     }
+    if (d->h_folded) (void)hipHostFree(d->h_folded);
+    if (d->ev_folded) (void)hipEventDestroy(d->ev_folded);
     if (d->h_counts) (void)hipHostFree(d->h_counts);
     if (d->ev_counts) (void)hipEventDestroy(d->ev_counts);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -1138,45 +1163,50 @@ static int ensure_pixel_sort(rt_device *d, uint32_t n_tiles, size_t pixels, hipS
     return RT_OK;
 }
 
-// rt_trace_tiles' selection bitmap of `words` words: the device copy and the two pinned slots a
-// new key's bitmap is uploaded from.  Growing waits first, as above (a copy out of a slot is work
-// of that stream too), so no slot is in flight afterwards.
-static int ensure_sel(rt_device *d, size_t words, hipStream_t sync, bool device_wide) {
-    if (words <= d->sel_cap) return RT_OK;
+// The selection buffer for images of up to `ref_tiles` reference tiles: the device copy of the
+// bitmap and of rt_trace_tile_work's counts table behind it, and the two pinned slots each of them
+// is uploaded from.  Growing waits first, as above (a copy out of a slot is work of that stream
+// too), so no slot is in flight afterwards.
+static int ensure_sel(rt_device *d, uint32_t ref_tiles, hipStream_t sync, bool device_wide) {
+    if (ref_tiles <= d->sel_cap) return RT_OK;
     if (device_wide) HIP_OK(hipDeviceSynchronize());
     else HIP_OK(hipStreamSynchronize(sync));
     (void)hipFree(d->d_sel);
     d->d_sel = nullptr;
     d->sel_cap = 0;
-    for (int i = 0; i < 2; ++i) {
-        if (d->h_sel[i]) (void)hipHostFree(d->h_sel[i]);
-        d->h_sel[i] = nullptr;
-        d->sel_in_flight[i] = false;
-        if (!d->ev_sel[i] && hipEventCreateWithFlags(&d->ev_sel[i], hipEventDisableTiming) != hipSuccess)
-            return fail(RT_ENOMEM, "rt_trace_tiles: selection upload event");
-    }
-    if (hipMalloc(&d->d_sel, words * 4u) != hipSuccess ||
-        hipHostMalloc(&d->h_sel[0], words * 4u, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&d->h_sel[1], words * 4u, hipHostMallocDefault) != hipSuccess)
-        return fail(RT_ENOMEM, "rt_trace_tiles: selection bitmap");
-    d->sel_cap = words;
+    const size_t slot_words[2] = {rtk_sel_table_at(ref_tiles), 2u * (size_t)ref_tiles};  // bitmap, table
+    StagedWords *staged[2] = {&d->sel, &d->counts};
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < 2; ++i) {
+            StagedWords &w = *staged[k];
+            if (w.h[i]) (void)hipHostFree(w.h[i]);
+            w.h[i] = nullptr;
+            w.in_flight[i] = false;
+            if (!w.ev[i] && hipEventCreateWithFlags(&w.ev[i], hipEventDisableTiming) != hipSuccess)
+                return fail(RT_ENOMEM, "rt_trace_tiles: upload event");
+            if (hipHostMalloc(&w.h[i], slot_words[k] * 4u, hipHostMallocDefault) != hipSuccess)
+                return fail(RT_ENOMEM, "rt_trace_tiles: pinned staging");
+        }
+    if (hipMalloc(&d->d_sel, rtk_sel_buffer_words(ref_tiles) * 4u) != hipSuccess)
+        return fail(RT_ENOMEM, "rt_trace_tiles: selection buffer");
+    d->sel_cap = ref_tiles;
     d->last.BufferGrowths += 1;
     d->tile_key.clear();
     return RT_OK;
 }
 
-// A new key's bitmap -> d_sel on `s`, through the pinned slot not used last.  The slot's previous
-// copy (two different lists ago) has normally finished long since; if not, the host waits for it
-// here -- the one place rt_trace_tiles may block beyond rt_trace's own.
-static int sel_upload(rt_device *d, const uint32_t *bits, size_t words, hipStream_t s) {
-    const uint32_t slot = d->sel_slot ^ 1u;
-    if (d->sel_in_flight[slot]) HIP_OK(hipEventSynchronize(d->ev_sel[slot]));
-    d->sel_in_flight[slot] = false;
-    memcpy(d->h_sel[slot], bits, words * 4u);
-    HIP_OK(hipMemcpyAsync(d->d_sel, d->h_sel[slot], words * 4u, hipMemcpyHostToDevice, s));
-    HIP_OK(hipEventRecord(d->ev_sel[slot], s));
-    d->sel_in_flight[slot] = true;
-    d->sel_slot = slot;
+// n words -> dst (device) on `s`, through the pinned slot not used last.  The slot's previous copy
+// (two uploads ago) has normally finished long since; if not, the host waits for it here -- the
+// one place rt_trace_tiles and rt_trace_tile_work may block beyond rt_trace's own.
+static int staged_upload(StagedWords &w, uint32_t *dst, const uint32_t *words, size_t n, hipStream_t s) {
+    const uint32_t slot = w.slot ^ 1u;
+    if (w.in_flight[slot]) HIP_OK(hipEventSynchronize(w.ev[slot]));
+    w.in_flight[slot] = false;
+    memcpy(w.h[slot], words, n * 4u);
+    HIP_OK(hipMemcpyAsync(dst, w.h[slot], n * 4u, hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(w.ev[slot], s));
+    w.in_flight[slot] = true;
+    w.slot = slot;
     return RT_OK;
 }
 
@@ -1190,7 +1220,7 @@ static int apply_reserve(rt_device *d) {
     if (d->scene_set)
         for (int rs = 0; rs < 2; ++rs) n_words = std::max(n_words, rtk_mask_words(d->n_groups[rs]));
     if (const int rc = ensure_tile_buffers(d, n_tiles, nullptr, true)) return rc;
-    if (const int rc = ensure_sel(d, d->reserve_sel_words, nullptr, true)) return rc;  // (rt_trace_tiles)
+    if (const int rc = ensure_sel(d, d->reserve_ref_tiles, nullptr, true)) return rc;  // (rt_trace_tiles, rt_trace_tile_work)
     if (d->pixel_sort_env)
         if (const int rc = ensure_pixel_sort(d, n_tiles, d->reserve_pixels, nullptr, true))
             return rc;
@@ -1206,8 +1236,8 @@ extern "C" int rt_device_reserve(rt_device *d, uint32_t width, uint32_t local_ro
     for (const int p : {1, 2, 4, 8, 16, 32}) n_tiles = std::max(n_tiles, rtk_tile_count(width, local_rows, p));
     d->reserve_tiles = std::max(d->reserve_tiles, n_tiles);
     d->reserve_pixels = std::max(d->reserve_pixels, (size_t)width * local_rows);
-    // (rt_trace_tiles' bitmap: one bit per reference tile of a width x local_rows image)
-    d->reserve_sel_words = std::max(d->reserve_sel_words, (size_t)(rt_tile_count(width, local_rows, nullptr) + 31u) / 32u);
+    // (rt_trace_tiles' bitmap and rt_trace_tile_work's table: the reference tiles of a width x local_rows image)
+    d->reserve_ref_tiles = std::max(d->reserve_ref_tiles, rt_tile_count(width, local_rows, nullptr));
     return apply_reserve(d);
 }
 
@@ -1224,7 +1254,7 @@ static_assert(kRefTile == RT_TILE_SIZE, "the kernels' reference tile is the head
 // size, how many tiles it names (the block tiles inside them, for any launch shape).
 struct TileSelection {
     const uint32_t *bits = nullptr;  // one bit per reference tile (TraceArgs.sel's layout)
-    uint32_t n_words = 0, tiles_x = 0;
+    uint32_t n_words = 0, tiles_x = 0, n_tiles = 0;  // bitmap words, TilesX, the image's reference tiles
     uint64_t pixels = 0;             // of the listed tiles, clipped to the image (main.cpp:362-368)
     // listed tiles by clipped size: [0] 32 x 32, [1] the ragged right column (clip_w x 32),
     // [2] the ragged bottom row (32 x clip_h), [3] the corner of both (clip_w x clip_h)
@@ -1238,6 +1268,13 @@ struct TileSelection {
     }
 };
 
+// A launch's per-tile counts (rt_trace_tile_work with mixed pairs): the table the kernels read
+// (TraceArgs.tile_counts_at's layout; {0, 0} for a tile outside the selection, which nothing reads).
+struct TileCounts {
+    const uint32_t *table = nullptr;
+    size_t n_words = 0;  // 2 x the image's reference tiles
+};
+
 // Validates a tile list against a width x height image and builds its bitmap into `bits`
 // (plain host code: no device, no allocation beyond the vector's growth).  Returns 0, or -1 for an
 // index past the image's tiles (*bad = its position in the list), -2 for an index named twice.
@@ -1249,6 +1286,7 @@ static int build_selection(const uint32_t *tiles, uint32_t n_tiles, uint32_t wid
     sel = TileSelection();
     sel.tiles_x = tiles_x;
     sel.n_words = (total + 31u) / 32u;
+    sel.n_tiles = total;
     sel.clip_w = width - (tiles_x - 1u) * RT_TILE_SIZE;   // the last column's and row's clipped
     sel.clip_h = height - (tiles_y - 1u) * RT_TILE_SIZE;  // size (32 when the image is not ragged)
     bits.assign(sel.n_words, 0u);
@@ -1288,8 +1326,12 @@ static int check_trace_args(rt_device *d, const rt_camera_info *cam, const rt_tr
 
 // rt_trace, over every tile of the band (sel == NULL) or over the listed reference tiles of the
 // full image (rt_trace_tiles: one band, sel validated against desc's image and not empty).
+// counts (rt_trace_tile_work with mixed pairs; needs sel): every listed tile folds its own frames from
+// its own count.  desc then carries the LARGEST Frames of the list, by which the launch shape is chosen
+// (never more lanes than frames; 4 pixels per lane at one frame), and PreviousRayCount 0; the kernels
+// take each tile's pair from the table.  Nothing of the counts enters the key.
 static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const TileSelection *sel,
-                        uint64_t *d_rays, void *stream) {
+                        const TileCounts *counts, uint64_t *d_rays, void *stream) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (const int rc = check_trace_args(d, cam, desc, d_rays)) return rc;
     const uint32_t band_rows = desc->BandRows ? desc->BandRows : 32u;
@@ -1426,6 +1468,13 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
         a.walk = rtk_walk_request(a, d->walk_any_env != 0);
     }
     const int src = a.scene_in_lds ? d->src : kSrcSmem;  // a scene in HBM is read through the scalar cache
+    if (counts && !a.solo && !rtk_tile_counts_four_wave(a.scene_in_lds, src)) {
+        // a four-wave launch whose kernel is not built with per-tile counts (SphereSourceLds, SceneInHbm,
+        // a scene beyond the LDS image): the one-wave run-time kernel, reported as such (rt_trace_info)
+        a.solo = 1u;
+        a.lut_in_lds = a.fold_in_lds = a.scene_in_lds = 0u;
+        a.walk = kWalkAny;
+    }
     const uint32_t n_tiles = rtk_tile_count(desc->Width, local_rows, lpp);
     // Units of the heaviest-first order: waves for the one-wave kernels (each wave
     // its own workgroup, so each is placed by its own cost), block tiles otherwise
@@ -1477,7 +1526,7 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     if (pixel_sort)
         if (const int rc = ensure_pixel_sort(d, n_tiles, (size_t)desc->Width * local_rows, s, false)) return rc;
     if (sel)
-        if (const int rc = ensure_sel(d, sel->n_words, s, false)) return rc;
+        if (const int rc = ensure_sel(d, sel->n_tiles, s, false)) return rc;
     const bool new_key = key != d->tile_key;
     // the key's bitmap on the device (uploaded below when the key is new; the same list again finds it there)
     a.sel = sel ? d->d_sel : nullptr;
@@ -1490,7 +1539,7 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
         // (first, so that a failed upload leaves no key behind that claims its bitmap is on the device)
         d->tile_key.clear();
         if (sel)
-            if (const int rc = sel_upload(d, sel->bits, sel->n_words, s)) return rc;
+            if (const int rc = staged_upload(d->sel, d->d_sel, sel->bits, sel->n_words, s)) return rc;
         d->tile_key = key;
         d->n_sorts = 0;
         if (pixel_sort) HIP_OK(hipMemsetAsync(d->d_pix_perm, 0xFF, (size_t)n_tiles * 64u, s));  // identity
@@ -1516,7 +1565,8 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
             // changes no bit: the owner lane folds frames in order either way, and
             // frame k's seed and weights depend on PreviousRayCount + k only.
             const uint32_t split_min = 4u * d->head_samples * lanes;
-            if (sched && d->split_env && desc->Frames >= split_min) {
+            // (not with per-tile counts: a split would need a head per tile)
+            if (sched && d->split_env && !counts && desc->Frames >= split_min) {
                 // leading parts of head_samples, x split_growth, ... samples per lane
                 // while the rest keeps at least half the frames
                 uint32_t f = d->head_samples * lanes, used = 0;
@@ -1558,6 +1608,10 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     const bool any_dead = empty_capable && (!known || d->n_live < n_selected);
     a.masks = cull ? d->d_masks : nullptr;
     a.tile_order = d->tile_order_valid ? d->d_tile_order : nullptr;
+    if (counts) {  // this call's table, whatever the key: the counts are no part of it
+        a.tile_counts_at = rtk_sel_table_at(sel->n_tiles);
+        if (const int rc = staged_upload(d->counts, d->d_sel + a.tile_counts_at, counts->table, counts->n_words, s)) return rc;
+    }
     // (the identity order knows no selection: both paths above leave a sorted order for a tile list)
     if (sel && !a.tile_order) return fail(RT_EIO, "rt_trace_tiles: no tile order for the selection");
     a.tile_cost = sched ? d->d_tile_cost : nullptr;
@@ -1579,6 +1633,8 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     d->last.GroupsPerRuleSet = a.n_groups;
     d->last.OneWaveGroups = a.solo;
     d->last.Walk = a.walk;
+    d->last_tile_counts = counts != nullptr;
+    d->last_folded_on_device = false;
     // one launch, or the split of a key's first launch (above): the leading
     // parts, then the rest, each continuing the running mean heaviest-first
     split[n_split++] = desc->Frames - head_frames;
@@ -1599,7 +1655,17 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
         a.tile_cost = resort ? d->d_tile_cost : nullptr;
         if (rtk_launch_trace_grid(&a, desc->EnableSIMD ? 1 : 0, src, cull ? 1 : 0, lpp, grid_tiles, s) != 0)
             return fail(RT_EIO, "rt_trace: kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-        if (any_dead && rtk_launch_empty(&a, lpp, d->d_tile_live, d->d_cull_counters + kCullTotals + 1, s) != 0)
+        if (any_dead && counts) {
+            // each dead tile folds by its own pair, and the device sums the segments (they are no longer
+            // dead pixels x frames); the sum follows to the host asynchronously, as the cull totals do
+            unsigned long long *folded = d->d_cull_counters + kCullFolded;
+            HIP_OK(hipMemsetAsync(folded, 0, sizeof(unsigned long long), s));
+            if (rtk_launch_empty_counts(&a, lpp, d->d_tile_live, folded, s) != 0)
+                return fail(RT_EIO, "rt_trace_tile_work: empty-tile launch failed: %s", hipGetErrorString(hipGetLastError()));
+            HIP_OK(hipMemcpyAsync(d->h_folded, folded, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            HIP_OK(hipEventRecord(d->ev_folded, s));
+            d->last_folded_on_device = true;
+        } else if (any_dead && rtk_launch_empty(&a, lpp, d->d_tile_live, d->d_cull_counters + kCullTotals + 1, s) != 0)
             return fail(RT_EIO, "rt_trace: empty-tile launch failed: %s", hipGetErrorString(hipGetLastError()));
         // the learned order settles within a few launches (C2: 7.7, 6.3, 6.1, 5.9,
         // 5.8 ms); after order_launches re-sorts (RT_ORDER_LAUNCHES, default 4)
@@ -1634,7 +1700,7 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
 
 extern "C" int rt_trace(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, uint64_t *d_rays,
                         void *stream) {
-    return trace_launch(d, cam, desc, nullptr, d_rays, stream);
+    return trace_launch(d, cam, desc, nullptr, nullptr, d_rays, stream);
 }
 
 extern "C" int rt_trace_tiles(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const uint32_t *tiles,
@@ -1653,7 +1719,62 @@ extern "C" int rt_trace_tiles(rt_device *d, const rt_camera_info *cam, const rt_
                     rt_tile_count(desc->Width, desc->Height, nullptr));
     if (v == -2) return fail(RT_EINVAL, "rt_trace_tiles: tiles[%u] = %u is listed twice", bad, tiles[bad]);
     if (n_tiles == 0 || desc->Frames == 0) return RT_OK;
-    return trace_launch(d, cam, desc, &sel, d_rays, stream);
+    return trace_launch(d, cam, desc, &sel, nullptr, d_rays, stream);
+}
+
+extern "C" int rt_trace_tile_work(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc,
+                                  const rt_tile_work *work, uint32_t n_work, uint64_t *d_rays, void *stream) {
+    if (!desc) return fail(RT_EINVAL, "rt_trace: NULL argument");
+    rt_trace_desc dd = *desc;  // (desc's own PreviousRayCount / Frames are not read: every entry has its pair)
+    dd.PreviousRayCount = 0;
+    dd.Frames = 0;
+    if (const int rc = check_trace_args(d, cam, &dd, d_rays)) return rc;
+    if (desc->BandCount > 1u || desc->BandIndex != 0u)
+        return fail(RT_EINVAL, "rt_trace_tile_work: tiles index the whole image (BandCount 0 or 1, BandIndex 0)");
+    if (!work && n_work) return fail(RT_EINVAL, "rt_trace_tile_work: work is NULL with n_work %u", n_work);
+    // every entry's tile first, those of zero-frame entries included: a tile named twice is refused
+    // before such entries are dropped.  The list is consumed here (the device's own host vectors; the
+    // uploads go through the library's pinned slots), so the caller's array is free on return.
+    TileSelection sel;
+    uint32_t bad = 0;
+    d->work_tiles.resize(n_work);
+    for (uint32_t i = 0; i < n_work; ++i) d->work_tiles[i] = work[i].Tile;
+    const int v = build_selection(d->work_tiles.data(), n_work, desc->Width, desc->Height, d->sel_bits, sel, &bad);
+    if (v == -1)
+        return fail(RT_EINVAL, "rt_trace_tile_work: work[%u].Tile = %u, the image has %u tiles", bad, work[bad].Tile,
+                    rt_tile_count(desc->Width, desc->Height, nullptr));
+    if (v == -2) return fail(RT_EINVAL, "rt_trace_tile_work: work[%u].Tile = %u is listed twice", bad, work[bad].Tile);
+    for (uint32_t i = 0; i < n_work; ++i)
+        if ((uint64_t)work[i].PreviousRayCount + work[i].Frames > 0xFFFFFFFFull)
+            return fail(RT_EINVAL, "rt_trace_tile_work: work[%u]: PreviousRayCount + Frames exceeds the u32 frame count", i);
+    // the kept entries (Frames > 0): their tiles, their table, whether they share one pair
+    const uint32_t total = rt_tile_count(desc->Width, desc->Height, nullptr);
+    d->counts_table.assign(2u * (size_t)total, 0u);
+    uint32_t kept = 0, max_frames = 0;
+    bool uniform = true;
+    const rt_tile_work *first = nullptr;
+    for (uint32_t i = 0; i < n_work; ++i) {
+        const rt_tile_work &e = work[i];
+        if (e.Frames == 0u) continue;
+        if (!first) first = &e;
+        uniform = uniform && e.PreviousRayCount == first->PreviousRayCount && e.Frames == first->Frames;
+        max_frames = std::max(max_frames, e.Frames);
+        d->counts_table[2u * (size_t)e.Tile] = e.PreviousRayCount;
+        d->counts_table[2u * (size_t)e.Tile + 1u] = e.Frames;
+        d->work_tiles[kept++] = e.Tile;
+    }
+    if (kept == 0) return RT_OK;
+    (void)build_selection(d->work_tiles.data(), kept, desc->Width, desc->Height, d->sel_bits, sel, &bad);
+    if (uniform) {  // one pair: rt_trace_tiles with it -- the same path, kernels and first-launch split
+        dd.PreviousRayCount = first->PreviousRayCount;
+        dd.Frames = first->Frames;
+        return trace_launch(d, cam, &dd, &sel, nullptr, d_rays, stream);
+    }
+    dd.Frames = max_frames;  // (the launch shape's frames; PreviousRayCount stays 0: every tile has its own)
+    TileCounts counts;
+    counts.table = d->counts_table.data();
+    counts.n_words = d->counts_table.size();
+    return trace_launch(d, cam, &dd, &sel, &counts, d_rays, stream);
 }
 
 extern "C" int rt_assemble_bands(const void *d_compact, uint64_t rank_stride_bytes, void *d_dst, uint32_t width,
@@ -1690,7 +1811,17 @@ extern "C" int rt_trace_last_info(rt_device *d, rt_trace_info *out) {
     d->last.TilesTraced = d->n_live;
     d->last.SegmentsFolded = d->last_empty_capable && d->n_live < d->last_n_tiles
                                  ? d->dead_pixels * d->last_frames : 0u;
+    if (d->last_folded_on_device) {  // per-tile counts: the device's own sum (waits for it, as above)
+        HIP_OK(hipEventSynchronize(d->ev_folded));
+        d->last.SegmentsFolded = *d->h_folded;
+    }
     *out = d->last;
+    return RT_OK;
+}
+
+extern "C" int rt_trace_last_tile_counts(rt_device *d, uint32_t *out) {
+    if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_tile_counts: NULL argument");
+    *out = d->last_tile_counts ? 1u : 0u;
     return RT_OK;
 }
 

@@ -1,5 +1,5 @@
 // rt_kernel.h — launch contract between the C-ABI host (rt_host.cpp) and the
-// gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_sched.hip).  Internal; not part of include/.
+// gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_trace_tc.hip, rt_sched.hip).  Internal; not part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -127,7 +127,29 @@ struct TraceArgs {
     // kernels see nothing but a shorter live prefix of tile_order.
     const uint32_t *sel;
     uint32_t sel_tiles_x;        // reference tiles per image row: ceil(width / kRefTile)
+    // optional (rt_trace_tile_work, with sel): each listed reference tile's own counts, two words per
+    // tile of the image -- {PreviousRayCount, Frames} at 2 * (TileY * sel_tiles_x + TileX) of the table
+    // rtk_tile_counts(a); 0 = none: the launch's prev_count / frames hold for every tile.  A block tile
+    // lies in one reference tile, so a wave takes one pair: the trace kernels compiled with
+    // kWalkTileCounts overwrite their by-value prev_count / frames with it before anything reads them,
+    // and rtk_launch_empty_counts folds each dead tile by its own pair.  Every listed tile's Frames is
+    // >= 1 (the host drops the others), and the launch's own frames field holds the largest of them.
+    // The table is named by its word offset from `sel` -- it lies behind the bitmap in the same device
+    // buffer (rtk_sel_table_at) -- and not by a pointer of its own, because a u32 fits the struct's tail
+    // padding: sizeof(TraceArgs) stays what it was, and with it the kernarg offsets of everything
+    // behind the struct (the scheduling kernels' other arguments, the hidden arguments the four-wave
+    // kernels read blockDim from).  An appended pointer moved those by 8 in every such kernel and
+    // renumbered select_kernel's SGPRs; this way no kernel of a uniform launch changes by a bit.
+    uint32_t tile_counts_at;
 };
+static_assert(sizeof(TraceArgs) == 360, "the kernarg layout of the kernels that take it (see tile_counts_at)");
+static inline __host__ __device__ const uint32_t *rtk_tile_counts(const TraceArgs &a) {
+    return a.tile_counts_at ? a.sel + a.tile_counts_at : nullptr;
+}
+// the selection buffer of an image of n reference tiles: the bitmap's words, then (8-byte aligned) the
+// counts table's 2 n words
+static inline uint32_t rtk_sel_table_at(uint32_t n_ref_tiles) { return 2u * ((n_ref_tiles + 63u) / 64u); }
+static inline size_t rtk_sel_buffer_words(uint32_t n_ref_tiles) { return rtk_sel_table_at(n_ref_tiles) + 2u * (size_t)n_ref_tiles; }
 constexpr uint32_t kRefTile = 32;  // the reference's TileSize (main.cpp:9; RT_TILE_SIZE of rt_trace.h)
 // live[] values of a block tile (rtk_launch_cull / rtk_launch_select): dead (folded by rtk_launch_empty),
 // live (traced), or outside the launch's tile selection (neither: no byte of it is written)
@@ -140,10 +162,19 @@ constexpr uint32_t kMergeGroups = 2;
 // (live tiles, dead pixels), summed on the device after the pass.
 constexpr uint32_t kCullCounterWords = 132;
 constexpr uint32_t kCullTotals = 128;
+constexpr uint32_t kCullFolded = 130;  // a per-tile launch's folded segments (rtk_launch_empty_counts), per launch
 // Secondary-ray walk variants (rtk_shape.h Walk<>): any (run-time dispatch),
 // the per-group loops, or a cluster walk with 1/2/4 pair-mask words and
 // scene-wide or per-lane ("Rel") thresholds
 enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWalkCl2Rel, kWalkCl4Rel };
+// Compile-time flag of trace_kernel, off in every value above: OR'ed into the kernel's WALK template
+// value it compiles the per-tile counts variant (TraceArgs.tile_counts_at).  A flag bit of an existing
+// parameter rather than a parameter of its own, so that the kernels without it keep their symbols.
+enum { kWalkMask = 0xFF, kWalkTileCounts = 0x100 };
+// The four-wave kernels exist with the flag for a scene in the LDS image read through the scalar cache
+// (the default four-wave device); a per-tile launch of any other four-wave device (SphereSourceLds,
+// SceneInHbm, a scene beyond the LDS image) runs the one-wave run-time kernel (rt_host.cpp).
+static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { return scene_in_lds != 0u && src == kSrcSmem; }
 
 // ---- Routing of the walk-specialised one-wave kernels (trace_kernel<..., SOLO = true, WALK != kWalkAny>).
 // Such a kernel holds one secondary walk and takes these facts of its launch at compile time
@@ -265,6 +296,11 @@ extern "C" int rtk_launch_encode_selected(const TraceArgs *a, hipStream_t stream
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:
 // the cull pass's device total, so the host need not read it back).
+// With a->tile_counts_at every dead block tile folds by its reference tile's own pair, and the segments
+// are summed on the device: in-image pixels x the tile's frames over the dead selected block tiles,
+// added to the ray counter and to *folded (required then; the caller zeroes it; dead_pixels is not read).
+extern "C" int rtk_launch_empty_counts(const TraceArgs *a, int lanes_per_pixel, const uint32_t *live,
+                                       unsigned long long *folded, hipStream_t stream);
 extern "C" int rtk_launch_empty(const TraceArgs *a, int lanes_per_pixel, const uint32_t *live,
                                 const unsigned long long *dead_pixels, hipStream_t stream);
 // Per block tile, deal its pixels to its four waves by the costs the last launch

@@ -275,6 +275,56 @@ __global__ __launch_bounds__(256) void empty_kernel(TraceArgs a, const uint32_t 
     if (!a.skip_cur) a.cur[pix] = rgba8(accx, accy, accz, (a.flags & kFlagSrgbPow) != 0u);
 }
 
+// empty_kernel for a launch with per-tile counts (TraceArgs.tile_counts_at): a dead block tile's pixels
+// fold by the {PreviousRayCount, Frames} pair of the reference tile around them, the ratios being
+// the same IEEE f32 quotients (a 256-pixel row segment spans up to eight reference tiles, so there
+// is no one table to stage).  The segments can no longer be one product: the thread on a dead block
+// tile's first pixel contributes in-image pixels x the tile's frames, a wave sums its lanes, and one
+// lane adds the sum to the ray counter and to *folded (rt_trace_info.SegmentsFolded).
+template <int P>
+__global__ __launch_bounds__(256) void empty_counts_kernel(TraceArgs a, const uint32_t *live,
+                                                           unsigned long long *folded) {
+    constexpr uint32_t BW = 2u * Shape<P>::TW, BH = 2u * Shape<P>::TH;
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, ly = blockIdx.y;
+    // (dead tiles only: a tile outside the launch's selection is kTileSkipped and keeps every byte)
+    const bool dead = x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == kTileDead;
+    uint32_t prev_count = 0, frames = 0;
+    if (dead) {  // (a dead tile is a selected one: its reference tile has a pair)
+        const uint32_t rt = (ly / kRefTile) * a.sel_tiles_x + x / kRefTile;
+        const uint32_t *pair = rtk_tile_counts(a) + 2u * rt;
+        prev_count = pair[0];
+        frames = pair[1];
+    }
+    unsigned long long seg = 0;
+    if (dead && x % BW == 0u && ly % BH == 0u)
+        seg = (unsigned long long)min(BW, a.width - x) * min(BH, a.local_rows - ly) * frames;
+    for (int off = 32; off > 0; off >>= 1) seg += __shfl_xor(seg, off);  // (every lane active)
+    if ((threadIdx.x & 63u) == 0u && seg) {
+        atomicAdd(a.rays, seg);
+        atomicAdd(folded, seg);
+    }
+    if (!dead) return;
+    const size_t pix = (size_t)ly * a.width + x;
+    float accx = 0.0f, accy = 0.0f, accz = 0.0f;
+    if (prev_count > 0 && !(a.flags & kFlagAccumZero)) {
+        const float4 pv = a.prev[pix];
+        accx = pv.x;
+        accy = pv.y;
+        accz = pv.z;
+    }
+    if (accx != 0.0f || accy != 0.0f || accz != 0.0f) {
+        for (uint32_t q = 0; q < frames; ++q) {
+            const uint32_t pc = prev_count + q;
+            const float r = (float)pc / (float)(pc + 1u);
+            accx = 0.0f + accx * r;
+            accy = 0.0f + accy * r;
+            accz = 0.0f + accz * r;
+        }
+    }
+    a.prev[pix] = make_float4(accx, accy, accz, 1.0f);
+    if (!a.skip_cur) a.cur[pix] = rgba8(accx, accy, accz, (a.flags & kFlagSrgbPow) != 0u);
+}
+
 // One wave per block tile: rank its pixels by the last launch's cost (ties by
 // index), so wave w of the next launch gets ranks [NPIX w, NPIX (w + 1)).
 // With pix_seg = S > 1 the ranked units are row segments of S pixels (summed
@@ -725,6 +775,20 @@ static void launch_empty_p(const TraceArgs *a, const uint32_t *live, const unsig
 extern "C" int rtk_launch_empty(const TraceArgs *a, int lanes_per_pixel, const uint32_t *live,
                                 const unsigned long long *dead_pixels, hipStream_t stream) {
     RTK_BY_P(launch_empty_p, a, live, dead_pixels, stream)
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+template <int P>
+static void launch_empty_counts_p(const TraceArgs *a, const uint32_t *live, unsigned long long *folded,
+                                  hipStream_t stream) {
+    hipLaunchKernelGGL(rtk::empty_counts_kernel<P>, dim3((a->width + 255u) / 256u, a->local_rows), dim3(256), 0,
+                       stream, *a, live, folded);
+}
+
+extern "C" int rtk_launch_empty_counts(const TraceArgs *a, int lanes_per_pixel, const uint32_t *live,
+                                       unsigned long long *folded, hipStream_t stream) {
+    if (!a->tile_counts_at || !a->sel || !folded) return -1;
+    RTK_BY_P(launch_empty_counts_p, a, live, folded, stream)
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -4,6 +4,11 @@
 extern "C" int rtk_launch_trace_grid(const TraceArgs *a, int simd, int src, int cull, int lanes_per_pixel,
                                      uint32_t n_blocks, hipStream_t stream) {
     if (n_blocks == 0) return 0;
+    if (a->tile_counts_at) {  // per-tile counts: the kernels compiled with kWalkTileCounts (rt_trace_tc.hip)
+        if (!a->sel) return -1;  // (the table is indexed by the selection's reference tiles)
+        rtk_launch_tile_counts(a, simd, src, cull, lanes_per_pixel, n_blocks, stream);
+        return hipGetLastError() == hipSuccess ? 0 : -5;
+    }
     switch (lanes_per_pixel) {
         case 32: launch_p<32>(a, simd, src, cull, n_blocks, stream); break;
         case 16: rtk_launch_p16(a, simd, src, cull, n_blocks, stream); break;  // (rt_trace_p16.hip)

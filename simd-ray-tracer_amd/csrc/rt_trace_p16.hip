@@ -10,3 +10,9 @@ extern "C" void rtk_launch_p16(const TraceArgs *a, int simd, int src, int cull, 
                                hipStream_t stream) {
     launch_p<16>(a, simd, src, cull, n_blocks, stream);
 }
+
+// the same shape with per-tile counts (rt_trace_tc.hip dispatches here)
+extern "C" void rtk_launch_p16_tile_counts(const TraceArgs *a, int simd, int src, int cull, uint32_t n_blocks,
+                                           hipStream_t stream) {
+    launch_p<16, kWalkTileCounts>(a, simd, src, cull, n_blocks, stream);
+}

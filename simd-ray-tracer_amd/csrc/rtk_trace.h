@@ -183,9 +183,16 @@ __device__ __forceinline__ void wave_unit(const Args &a, uint32_t tid, uint32_t 
 // pressure of the others out of the trace loop (C2 +4 % with only the W = 1
 // walk compiled in).  The exact all-groups loop stays in every variant (rounds
 // whose directions leave the prefilter's |D|^2 bound).
-template <bool SIMD, int SRC, bool CULL, int P, bool GS, bool SOLO = false, int WALK = kWalkAny>
-__global__ __launch_bounds__(SOLO ? 64 : 256, SOLO ? solo_waves(WALK) : SRC == kSrcSmem ? RTK_MIN_WAVES_PER_SIMD : 1)
+// WALKF: the walk, and with kWalkTileCounts OR'ed in the per-tile counts variant (rt_trace_tile_work):
+// once the wave knows its block tile it takes the {PreviousRayCount, Frames} pair of the reference
+// tile around it from the table rtk_tile_counts(a) (scalar loads) and overwrites its by-value a.prev_count /
+// a.frames; nothing after that point differs.  The flag is off in every kWalk* value, so the kernels
+// of uniform launches are the ones they were, symbol and code.
+template <bool SIMD, int SRC, bool CULL, int P, bool GS, bool SOLO = false, int WALKF = kWalkAny>
+__global__ __launch_bounds__(SOLO ? 64 : 256, SOLO ? solo_waves(WALKF & kWalkMask) : SRC == kSrcSmem ? RTK_MIN_WAVES_PER_SIMD : 1)
 void trace_kernel(TraceArgs a) {
+    constexpr int WALK = WALKF & kWalkMask;
+    constexpr bool kTileCounts = (WALKF & kWalkTileCounts) != 0;
     static_assert(!GS || SRC == kSrcSmem, "a scene in HBM is read through the scalar cache");
     static_assert(!SOLO || GS, "a one-wave workgroup keeps no LDS image");
     constexpr uint32_t kWB = SOLO ? 1u : (uint32_t)kWavesPerBlock;  // waves (LDS slots) per workgroup
@@ -217,6 +224,22 @@ void trace_kernel(TraceArgs a) {
     // first launch of a key: the host has not read the live-tile count back, so
     // the grid covers every tile (live first) and blocks past the count leave
     if (a.live_total && (SOLO ? blockIdx.x >> 2 : blockIdx.x) >= (uint32_t)*a.live_total) return;
+    if constexpr (kTileCounts) {
+        // The block tile's own counts.  Taken first: the fold table below is filled from a.prev_count,
+        // and every later reader (the mean's load, the sample hand-out, the weights, the fold and the ray
+        // count) sees the pair as if the launch had carried it.  The block tile is workgroup-uniform
+        // (wave_unit: one tile per four-wave workgroup, one wave per one-wave workgroup) and lies in one
+        // reference tile (rtk_shape.h), as do a pixel-sorted wave's pixels and a P = 0 lane's four.
+        uint32_t t0, w0;
+        wave_unit<SOLO>(a, threadIdx.x, t0, w0);
+        const uint32_t rt = (((t0 / a.tiles_x) * (2u * Shape<P>::TH)) / kRefTile) * a.sel_tiles_x +
+                            ((t0 % a.tiles_x) * (2u * Shape<P>::TW)) / kRefTile;
+        const uint32_t *pair = a.sel + a.tile_counts_at + 2u * rt;  // (rtk_tile_counts: the host launches these kernels with a table)
+        a.prev_count = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair[0]);
+        a.frames = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair[1]);
+        // (the host lists no tile with Frames == 0: the launch fact of the walk kernels holds per tile)
+        if constexpr (SOLO && WALK != kWalkAny) __builtin_assume(a.frames != 0u);
+    }
     TraceStats<kStats> st(a.stats);  // (the -DRTK_STATS build's counters; empty otherwise)
     // LDS image: [rsqrt table 512 float4][fold table 128 float4]
     //            [groups kGroupF4*n_groups float4][sphere records kSphereF4*4*n_groups float4]
@@ -809,14 +832,18 @@ void trace_kernel(TraceArgs a) {
 
 }  // namespace rtk
 
-template <int P>
+// F: 0, or kWalkTileCounts for a launch with per-tile counts (a->tile_counts_at set).  Each translation
+// unit instantiates the F it launches: the per-tile kernels are compiled in units of their own
+// (rt_trace_tc.hip; P = 16 beside the uniform ones in rt_trace_p16.hip), in parallel with these.
+template <int P, int F = 0>
 static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n_blocks, hipStream_t stream) {
     const dim3 block(256), grid(n_blocks);
     const size_t lds = rtk_lds_bytes(a);
     const size_t solo_lds = 8u * rtk_mask_words(a->n_groups);  // one-wave kernels: the cull mask words
-#define RTK_LAUNCH(S, R, C, G) hipLaunchKernelGGL((rtk::trace_kernel<S, R, C, P, G>), grid, block, lds, stream, *a)
+#define RTK_LAUNCH(S, R, C, G) \
+    hipLaunchKernelGGL((rtk::trace_kernel<S, R, C, P, G, false, F>), grid, block, lds, stream, *a)
 #define RTK_LAUNCH_SOLO(S, C, K) \
-    hipLaunchKernelGGL((rtk::trace_kernel<S, kSrcSmem, C, P, true, true, K>), dim3(4u * n_blocks), dim3(64), solo_lds, \
+    hipLaunchKernelGGL((rtk::trace_kernel<S, kSrcSmem, C, P, true, true, (K) | F>), dim3(4u * n_blocks), dim3(64), solo_lds, \
                        stream, *a)
     if (a->solo) {  // one wave per workgroup, no LDS image (the host clears the *_in_lds flags)
         // One walk per kernel where the launch has every fact such a kernel takes at compile time; else
@@ -847,6 +874,19 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
         return;
     }
 #undef RTK_LAUNCH_SOLO
+    if constexpr (F != 0) {
+        // Four-wave per-tile kernels exist for a scene in the LDS image read through the scalar cache
+        // only (rt_kernel.h rtk_tile_counts_four_wave): the host routes every other four-wave
+        // per-tile launch to the one-wave run-time kernel above, so nothing else arrives here.
+        const int key = (simd ? 2 : 0) | (cull ? 1 : 0);
+        switch (key) {
+            case 0: RTK_LAUNCH(false, kSrcSmem, false, false); break;
+            case 1: RTK_LAUNCH(false, kSrcSmem, true, false); break;
+            case 2: RTK_LAUNCH(true, kSrcSmem, false, false); break;
+            default: RTK_LAUNCH(true, kSrcSmem, true, false); break;
+        }
+        return;
+    } else {
     if (!a->scene_in_lds) {  // the scene in HBM (the host picks the SMEM source for it)
         const int key = (simd ? 2 : 0) | (cull ? 1 : 0);
         switch (key) {
@@ -868,9 +908,13 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
         case 6: RTK_LAUNCH(true, kSrcLds, false, false); break;
         default: RTK_LAUNCH(true, kSrcLds, true, false); break;
     }
+    }
 #undef RTK_LAUNCH
 }
 
-// The P = 16 launches are compiled in a translation unit of their own (rt_trace_p16.hip)
+// The P = 16 launches are compiled in a translation unit of their own (rt_trace_p16.hip), the
+// launches with per-tile counts of every other shape in another (rt_trace_tc.hip)
 extern "C" void rtk_launch_p16(const TraceArgs *a, int simd, int src, int cull, uint32_t n_blocks,
                                hipStream_t stream);
+extern "C" void rtk_launch_tile_counts(const TraceArgs *a, int simd, int src, int cull, int lanes_per_pixel,
+                                       uint32_t n_blocks, hipStream_t stream);
