@@ -623,6 +623,14 @@ int64_t rt_debug_masks(rt_device *dev, uint64_t *out, uint64_t max_words);
  * Arrays may be NULL to query the count. */
 int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, float *out_r2, float *out_r2p, uint32_t capacity,
                        uint32_t *out_count, uint32_t *out_flags);
+/* The own-sphere rule's per-slot word (test/inspection hook; DESIGN.md §3, "the sphere a ray
+ * leaves"): out_rho[s] is word 3 of sphere s's record, r_s^2 where a lane may prove that the ray it
+ * continues from sphere s cannot accept s again, +inf where nothing is proven (no scene-wide
+ * cluster table, a sphere outside it, a radius outside [16.1 eps, 16]).  A lane with C = RN(S - O),
+ * cc = fma |C|^2 and T = fma C.D leaves s out of its own member flags when
+ * |RN(rho - cc (1 - 5 2^-18))| < RN(-T 1.9e-4).  out_rho may be NULL to query the count. */
+int rt_scene_own_sphere(const rt_scene *scene, uint32_t enable_simd, float *out_rho, uint32_t capacity,
+                        uint32_t *out_count);
 /* The packed sphere-group records rt_scene_upload builds for one rule set, as
  * the device reads them (layout: rt_kernel.h, "HBM layout of an uploaded
  * scene").  *out_f4 = float4 rows; out_rows (optional, 6 words) = rows per

@@ -208,6 +208,7 @@ SIGNATURES = {
     "rt_debug_masks": (ctypes.c_int64, [c_void_p, c_void_p, c_uint64]),
     "rt_scene_prefilter": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_void_p, c_uint32, POINTER(c_uint32),
                                    POINTER(c_uint32)]),
+    "rt_scene_own_sphere": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32)]),
     "rt_scene_clusters": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32),
                                   POINTER(c_uint32)]),
     "rt_scene_groups": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32), c_void_p]),
@@ -382,6 +383,17 @@ def scene_prefilter(scene: RtScene, simd: bool = True):
     _check(lib().rt_scene_prefilter(ctypes.byref(scene), int(simd), r2.ctypes.data, r2p.ctypes.data, n.value,
                                     ctypes.byref(n), ctypes.byref(fl)), "rt_scene_prefilter")
     return r2, r2p, int(fl.value)
+
+
+def scene_own_sphere(scene: RtScene, simd: bool = True) -> np.ndarray:
+    """rho per sphere slot 4*group+lane (rt_scene_own_sphere): r^2 where the own-sphere rule of the
+    cluster walk applies to the sphere, +inf where it is off."""
+    n = c_uint32()
+    _check(lib().rt_scene_own_sphere(ctypes.byref(scene), int(simd), None, 0, ctypes.byref(n)), "rt_scene_own_sphere")
+    rho = np.zeros(n.value, np.float32)
+    _check(lib().rt_scene_own_sphere(ctypes.byref(scene), int(simd), rho.ctypes.data, n.value, ctypes.byref(n)),
+           "rt_scene_own_sphere")
+    return rho
 
 
 def scene_groups(scene: RtScene, simd: bool = True):

@@ -407,7 +407,7 @@ extern "C" int rt_set_rsqrt_table(rt_device *d, const float table[2048]) {
 }
 
 // Packs one rule set: positions/radii as 4-wide groups with r*r precomputed,
-// sphere records as {centre.xyz, 0}, {Color.xyz, Specular}, {Emissive.xyz, IOR}, {0} (kSphereF4).
+// sphere records as {centre.xyz, rho}, {Color.xyz, Specular}, {Emissive.xyz, IOR}, {0} (kSphereF4).
 static int upload_set(rt_device *d, int rs, const std::vector<float> &groups, const std::vector<float> &mats,
                       uint32_t n_groups) {
     if (n_groups > d->cap_groups[rs]) {
@@ -539,12 +539,52 @@ static bool prefilter_rows(std::vector<float> &gv, uint32_t n_groups, bool simd)
 //   cluster  -(max_j ((delta_j + r_j)(1 + 2^-15) + 4.3u delta_j) + 4.3u),
 //   member   -(r_j (1 + 2^-15) + 4.3u),
 // and a lane's behind test is T < RN(stored - 4.5u cc).
+//
+// Own sphere (scene-wide tables; rtk_walk.h own_sphere).  A lane that continues a path from sphere j
+// (slot j: word 2 / 3 of row 3 of j's member entry) leaves j out of its own member flags when
+//   |d| < RN(-T lambda),   d = RN(rho_j - cc kappa),   kappa = 1 - 320u,  lambda = 1.9 eps,
+// with C = RN(S_j - O) per axis -- the reference's own C_j, bit for bit -- and the FMA values
+// cc ~ |C|^2, T ~ C.D of pair_prefilter; rho_j = r_j^2 (the f32 the exact test compares with; word 3
+// of the record's centre row) for the table's members with r_j^2 in [kOwnR2Min, kOwnR2Max], else +inf
+// (d = +inf or NaN: never).  Everything below is a function of C, D and r_j^2 alone, so nothing is
+// assumed about the segment that led to O (its length, its direction's norm, which root was taken, how
+// O was rounded): the test measures how far O lies off the sphere instead of bounding it.
+// Claim: under the rule the reference's candidate j (main.cpp:413-429, 561-578) is rejected by both
+// rule sets whatever the running minima are: if dist_r <= r^2 at all, then RN(T_r - X_r) < eps and
+// RN(T_r + X_r) < eps strictly (SIMD accepts only it > eps, scalar only !(it < eps)).
+// With a = |C|, c* = a^2, T* = C.D exact, |D|^2 = 1 + k, |k| <= K = 2^-16, u = 2^-24:
+//  (1) the lane's values: cc within 3.01u c* of c*, T within 3.01u a|D| of T*.  The rule gives T < 0
+//      and |d| < 2.001 a eps, so |r^2 - c*| <= 2.01 a eps + 324u c*: with r in [16.1 eps, 16],
+//      14.9 eps <= a <= 16.01 (no product underflows, and 3.01u a <= 0.029 eps);
+//  (2) the reference: T_r = dot3 within 3.01u a of T*; its dist_r (exact ops on C) is within 8u c* of
+//      |C - D T_r|^2 >= c* - T*^2 / (1 + k) (q's two roundings 4.1u c*, the dot's three 3.1u c*:
+//      the 13.3u M term above with M = c*), so
+//        r^2 - dist_r <= r^2 - c* (1 - 8u - 1.03K) + T*^2;
+//      X_r = RN(sqrt(RN(r^2 - dist_r))) <= sqrt((r^2 - dist_r)(1 + 3.3u)), and by (1)
+//      3.3u (r^2 - dist_r) <= 3.4u c* + 6.7u a eps, so X_r^2 <= T*^2 + Delta,
+//        Delta = r^2 - c* (1 - 11.4u - 1.03K) + 6.7u a eps;
+//  (3) kappa: cc kappa <= c* (1 + 3.01u)(1 - 320u) <= c* (1 - 316u), and 1.03K + 11.4u = 275.1u, so
+//      rho - cc kappa >= Delta + 40u c*  (6.7u a eps <= 0.45u c* by a >= 14.9 eps);
+//  (4) Delta <= 0: X_r <= |T*|, T_r + X_r <= 3.01u a <= 0.029 eps.  Else sqrt(T*^2 + Delta) <=
+//      |T*| + Delta / (2|T*|) and the rule gives Delta + 40u c* <= d (1 + u) < |T| lambda (1 + 2.1u)
+//      <= (|T*| + 3.01u a) lambda (1 + 2.1u), where 3.01u a lambda (1 + 2.1u) <= 0.4u c* is inside the
+//      40u c*: Delta < |T*| lambda (1 + 2.1u), hence
+//        T_r + X_r <= 3.01u a + lambda (1 + 2.1u) / 2 <= 0.029 eps + 0.9501 eps < eps (1 - 2u),
+//      and RN of a sum below eps (1 - 2u) is below eps; T_r - X_r <= T_r + X_r.  dist_r == r^2 (the
+//      scalar rules' hit) has X_r = 0 and T_r <= 0.029 eps + T* < eps.
+// The square root is the reference's correctly rounded one; the kernel's own candidate code is not
+// involved -- a dropped lane runs no candidate for j unless another lane flags the pair, and then its
+// exact test reproduces this rejection.  tests/test_own_sphere_skip.py checks the claim on rays formed
+// as the reference forms them.
 // k_override / sub_override: rt_device_options ClusterCount / SubClusterSpheres (0: per scene, below).
+constexpr float kOwnR2Min = 2.6e-6f, kOwnR2Max = 256.0f;  // r in [16.1 eps, 16]
 static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, std::vector<float> &tab,
                               uint32_t *words, bool relative = false, uint32_t *levels = nullptr,
-                              uint32_t *sub_pairs = nullptr, uint32_t k_override = 0, uint32_t sub_override = 0) {
+                              uint32_t *sub_pairs = nullptr, uint32_t k_override = 0, uint32_t sub_override = 0,
+                              std::vector<float> *own_rho = nullptr) {
     if (levels) *levels = 0;
     if (sub_pairs) *sub_pairs = 0;
+    if (own_rho) own_rho->assign(4u * (size_t)n_groups, INFINITY);
     tab.clear();
     *words = n_groups <= 32u ? 1u : n_groups <= 64u ? 2u : 4u;
     if (n_groups > kClMaxGroups) return 0;
@@ -843,6 +883,7 @@ static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, s
                     m[4 + w] = sphere_xyz(s, kRowZ);
                     m[6 + w] = sphere_r2p(s);
                     m[12 + w] = beta_of_slot[s];
+                    if (!relative) put_u(mb + 14u + (uint32_t)w, s);  // its slot (the own-sphere rule)
                     // the u64 bit of pair q = s >> 1 in the row of word q >> 6 (row 2
                     // for word 0, row 3 + w for word w >= 1; the other words' rows stay 0)
                     const uint64_t bit = 1ull << ((s >> 1) & 63u);
@@ -881,6 +922,12 @@ static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, s
             }
         }
     }
+    // the own-sphere rule's rho_j (above): r_j^2 for the members inside the proven radius range
+    if (own_rho && !relative)
+        for (const Sph &o : sp) {
+            const float r2 = gv[(o.s / 4u) * 4u * kGroupF4 + 4u * kRowR2 + o.s % 4u];
+            if (r2 >= kOwnR2Min && r2 <= kOwnR2Max) (*own_rho)[o.s] = r2;
+        }
     if (levels) *levels = two ? 2u : 1u;
     if (sub_pairs) *sub_pairs = n_sp;
     return n_cp;
@@ -912,6 +959,7 @@ struct PackedSet {
     std::vector<float> clusters;  // cluster_table
     uint32_t n_cpairs = 0, cl_words = 0;
     uint32_t cl_levels = 0, cl_sub_pairs = 0;  // two-level tables (cl_words >= 2)
+    std::vector<float> own_rho;  // per slot: word 3 of the sphere record's centre row (cluster_table, "own sphere")
 };
 
 static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env = -1, uint32_t cluster_k = 0,
@@ -969,7 +1017,9 @@ static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env 
     // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
     p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
     p.n_cpairs = cluster_table(gv, n, p.clusters, &p.cl_words, p.relative, &p.cl_levels, &p.cl_sub_pairs, cluster_k,
-                               sub_spheres);
+                               sub_spheres, &p.own_rho);
+    // (a record per real sphere of the scalar set, per slot of the SIMD set; without a table every rho is +inf)
+    for (uint32_t sl = 0; sl < (rs == 0 ? 4u * n : ns); ++sl) p.mats[(size_t)sl * 4u * kSphereF4 + 3u] = p.own_rho[sl];
     if (p.relative)
         for (uint32_t sl = 0; sl < 4u * n; ++sl) {
             const size_t base = (size_t)(sl / 4u) * 4u * kGroupF4 + sl % 4u;
@@ -1045,6 +1095,19 @@ extern "C" int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, f
         if (out_r2) out_r2[s] = p.groups[base + 4u * kRowR2];
         if (out_r2p) out_r2p[s] = p.groups[base + 4u * kRowR2P];
     }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_own_sphere(const rt_scene *scene, uint32_t enable_simd, float *out_rho, uint32_t capacity,
+                                   uint32_t *out_count) {
+    if (!scene || !out_count) return fail(RT_EINVAL, "rt_scene_own_sphere: NULL argument");
+    PackedSet p;
+    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
+    if (rc) return rc;
+    const uint32_t n = 4u * p.n_groups;
+    *out_count = n;
+    if (out_rho && capacity < n) return fail(RT_EINVAL, "rt_scene_own_sphere: capacity %u < %u", capacity, n);
+    for (uint32_t s = 0; out_rho && s < n; ++s) out_rho[s] = p.own_rho[s];
     return RT_OK;
 }
 

@@ -16,7 +16,9 @@ enum { kFlagAccumZero = 1, kFlagSrgbPow = 2 };
 // cl_entry_f4(W) float4 rows, read through the scalar cache --
 //   cluster pair c : {qx0 qx1 qy0 qy1} {qz0 qz1 rc2p0 rc2p1} {first0 count0 first1 count1} {b0 b1 0 0} [padding]
 //   member pair m  : {x0 x1 y0 y1}     {z0 z1 r2p0 r2p1}     {word-0 bits of member 0 (lo, hi), of member 1}
-//                    {b0 b1 0 0}  then one row per further word w = 1 .. W-1: {word-w bits of member 0, of member 1}
+//                    {b0 b1 slot0 slot1}  then one row per further word w = 1 .. W-1: {word-w bits of member 0, of member 1}
+// (slot = the member's sphere slot 4*group + lane as a u32, scene-wide tables only (else 0): a lane that has
+// proven it cannot accept the sphere its ray leaves drops that slot from its own flags -- rtk_walk.h own_sphere)
 // (b = behind threshold: a lane whose prefilter T = (centre - O).D is below
 // it cannot accept any member -- rt_host.cpp cluster_table)
 // (first/count index member-pair entries; a member's pair q = sphere slot >> 1
@@ -44,8 +46,10 @@ constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_
 //               rows 0-3 are what an exact test reads (the cluster walk's recheck: one scalar load);
 //               r2p = prefilter threshold of the secondary-ray sphere loop (rt_host.cpp);
 //               with pf_relative, r*r again (-inf: never hit) and the threshold is formed per lane
-//   spheres   : 4*n_groups records of kSphereF4 float4 = {centre.xyz, 0}, {Color.xyz, Specular},
+//   spheres   : 4*n_groups records of kSphereF4 float4 = {centre.xyz, rho}, {Color.xyz, Specular},
 //               {Emissive.xyz, IOR}, {1/IOR, r0 outside, r0 inside, 0} (dielectrics; else 0)
+//               rho = r*r where the own-sphere rule applies to the sphere, +inf where it is off
+//               (rt_host.cpp cluster_table, "own sphere"; rt_scene_own_sphere reports it)
 //               (64 B/sphere: what shading gathers for the winning sphere,
 //               addressed by one shift of its index; TraceArgs.materials)
 // r*r is precomputed on the host with the same f32 multiply the reference

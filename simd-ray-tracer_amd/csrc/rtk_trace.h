@@ -457,7 +457,11 @@ void trace_kernel(TraceArgs a) {
     uint32_t pend_s = 0u;
     // Re-derive the winner's HitNormal / NextRayOrigin exactly as they were
     // formed at acceptance (main.cpp:423-429), then shade and bounce.
-    auto shade_hit = [&](float tmin, uint32_t sidx, bool inside) {
+    // Returns the slot the continued ray leaves and cannot accept (rtk_walk.h own_sphere: formed from the
+    // centre row loaded here and the ray shade has just made), for the kernels that hold a scene-wide
+    // cluster walk; kOwnNone in every other kernel, which computes nothing for it.
+    constexpr bool kOwnRule = Walk<WALK>::CLUSTERS ? !Walk<WALK>::REL : WALK == kWalkAny;
+    auto shade_hit = [&](float tmin, uint32_t sidx, bool inside) -> uint32_t {
         // the winner's record (rt_kernel.h kSphereF4): one shift of the sphere index addresses its
         // centre and both material rows
         const float4 *rec = mat_src + kSphereF4 * sidx;
@@ -473,6 +477,15 @@ void trace_kernel(TraceArgs a) {
         const float4 ei = rec[2];
         shade(lut, cs, ei, rec + 3, hx, hy, hz, inside, p);
         p.bounce += 1;
+        if constexpr (kOwnRule) {
+            // (the centre row is read again rather than held across shade: four VGPRs there; the index is
+            // made opaque so that the two loads stay two)
+            uint32_t again = sidx;
+            asm volatile("" : "+v"(again));
+            return own_sphere(p, mat_src[kSphereF4 * again], sidx);
+        } else {
+            return kOwnNone;
+        }
     };
     // the pixel's owner lane's fold cursor (first of its P-lane slice) via DPP
     auto fold_cursor = [&]() -> uint32_t {
@@ -637,8 +650,9 @@ void trace_kernel(TraceArgs a) {
                 pseg += 1u;
                 // The round's lanes are in mode 1 (a pending hit to shade) or 0 (a sample to start).  Split
                 // rounds hold one kind, so the choice is the round's own; merged rounds hold both.
+                uint32_t own = kOwnNone;  // (lives for this round only: pend_s is dead once shaded)
                 if (kMergeable ? mode == 1u : do_sec != 0u)
-                    shade_hit(pend_t, pend_s & ~kPendInside, (pend_s & kPendInside) != 0u);
+                    own = shade_hit(pend_t, pend_s & ~kPendInside, (pend_s & kPendInside) != 0u);
                 else
                     start_sample(kernel_args(), x, y, a.prev_count + k, p);
                 bool done;
@@ -678,17 +692,17 @@ void trace_kernel(TraceArgs a) {
                         if (SRC == kSrcSmem && pf && (Walk<WALK>::CLUSTERS || a.n_cpairs)) {
                             PfStats *ps = st.pf_round();
                             if constexpr (Walk<WALK>::CLUSTERS) {
-                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL>(a, lds_groups, ray, h, fast, ps);
+                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL>(a, lds_groups, ray, h, fast, own, ps);
                             } else if constexpr (WALK == kWalkGroups) {
                                 __builtin_unreachable();  // the host runs kWalkGroups kernels without a cluster table
                             } else if (a.pf_relative) {
-                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, true>(a, lds_groups, ray, h, fast, ps);
-                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, true>(a, lds_groups, ray, h, fast, ps);
-                                else clustered_groups<SIMD, 4, GS, true>(a, lds_groups, ray, h, fast, ps);
+                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, true>(a, lds_groups, ray, h, fast, own, ps);
+                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, true>(a, lds_groups, ray, h, fast, own, ps);
+                                else clustered_groups<SIMD, 4, GS, true>(a, lds_groups, ray, h, fast, own, ps);
                             } else {
-                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, false>(a, lds_groups, ray, h, fast, ps);
-                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, false>(a, lds_groups, ray, h, fast, ps);
-                                else clustered_groups<SIMD, 4, GS, false>(a, lds_groups, ray, h, fast, ps);
+                                if (a.cl_words == 1u) clustered_groups<SIMD, 1, GS, false>(a, lds_groups, ray, h, fast, own, ps);
+                                else if (a.cl_words == 2u) clustered_groups<SIMD, 2, GS, false>(a, lds_groups, ray, h, fast, own, ps);
+                                else clustered_groups<SIMD, 4, GS, false>(a, lds_groups, ray, h, fast, own, ps);
                             }
                         } else if (SRC == kSrcSmem && pf && a.pf_relative && !Walk<WALK>::CLUSTERS) {
                             all_groups_smem<SIMD, true, GS, true>(a, lds_groups, ray, h, fast, nullptr, st.pf_round());

@@ -396,17 +396,21 @@ __device__ __forceinline__ void merge_words(uint64_t (&wave)[kClWords], uint64_t
 // lane-mask conjunction's own SCC (result != 0) feeds the 64-bit select, so a member
 // costs and + select + or on the scalar unit (the compiler's lowering: and, compare,
 // two 32-bit selects, or; C2 +1.6 % over it, profiles/r07a_scalar_diet_ab.txt).
-__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t n0, uint64_t k0, uint64_t bits0, uint64_t n1,
-                                            uint64_t k1, uint64_t bits1) {
+// (x0, x1: the lanes that do not leave this member -- own_sphere below; one more conjunction each)
+__device__ __forceinline__ void merge_word1(uint64_t &wave, uint64_t n0, uint64_t k0, uint64_t x0, uint64_t bits0,
+                                            uint64_t n1, uint64_t k1, uint64_t x1, uint64_t bits1) {
     uint64_t t;
     asm("s_and_b64 %[t], %[n0], %[k0]\n\t"
+        "s_and_b64 %[t], %[t], %[x0]\n\t"
         "s_cselect_b64 %[t], %[b0], 0\n\t"
         "s_or_b64 %[w], %[w], %[t]\n\t"
         "s_and_b64 %[t], %[n1], %[k1]\n\t"
+        "s_and_b64 %[t], %[t], %[x1]\n\t"
         "s_cselect_b64 %[t], %[b1], 0\n\t"
         "s_or_b64 %[w], %[w], %[t]"
         : [w] "+&s"(wave), [t] "=&s"(t)
-        : [n0] "s"(n0), [k0] "s"(k0), [b0] "s"(bits0), [n1] "s"(n1), [k1] "s"(k1), [b1] "s"(bits1)
+        : [n0] "s"(n0), [k0] "s"(k0), [x0] "s"(x0), [b0] "s"(bits0), [n1] "s"(n1), [k1] "s"(k1), [x1] "s"(x1),
+          [b1] "s"(bits1)
         : "scc");
 }
 // (single lane masks: per-lane tables test no behind rule at the member level)
@@ -477,9 +481,33 @@ __device__ __forceinline__ void cluster_slab(f2 cc, f2 T, const RayPk &ray, cons
           [T] "v"(T), [ymid] "s"(ymid));
 }
 
+// The sphere a secondary ray leaves (scene-wide tables; rt_host.cpp cluster_table proves it, "own
+// sphere").  The ray's origin lies on sphere j, so the near-line estimate always flags j and the
+// behind rule never clears it (T >= -r against b < -r), yet the candidate is rejected: T - X < eps
+// turns it into T + X ~ 0.  A lane proves that for itself from the ray it has: with C = RN(S_j - O)
+// (the reference's own C_j, bit for bit), cc = |C|^2 and T = C.D as pair_prefilter forms them,
+//   |RN(rho_j - cc kOwnCc)| < RN(-T kOwnLam)          rho_j = r_j^2, or +inf where nothing is proven
+// shows that the reference's candidate j has T + X < eps: rejected under both rule sets whatever the
+// running minima are.  Such a lane leaves slot j out of its own member flag (the value returned
+// here; kOwnNone: no slot).  The wave's mask stays the union over lanes, and a lane still runs the
+// exact test of j when another lane flags the pair, which reproduces the rejection.
+// The test measures how far the origin lies off the sphere (rho - cc) rather than bounding it, so it
+// assumes nothing about the segment that led here, only |D|^2 within 2^-16 of 1 (every prefiltered round).
+constexpr uint32_t kOwnNone = 0xFFFFFFFFu;
+constexpr float kOwnCc = 1.0f - 5.0f * 0x1p-18f;  // 1 - 1.25K: K T^2 and the roundings of dist, cc and X
+constexpr float kOwnLam = 1.9e-4f;                // 1.9 eps of the 2 eps the square root's slope allows
+__device__ __forceinline__ uint32_t own_sphere(const Sample &p, float4 sc, uint32_t slot) {
+    const float cx = sc.x - p.rx.x, cy = sc.y - p.ry.x, cz = sc.z - p.rz.x;
+    const float cc = __builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz));
+    const float T = __builtin_fmaf(cz, p.rz.y, __builtin_fmaf(cy, p.ry.y, cx * p.rx.y));
+    const float d = __builtin_fmaf(cc, -kOwnCc, sc.w);
+    return __builtin_fabsf(d) < T * -kOwnLam ? slot : kOwnNone;
+}
+
+// own (scene-wide tables): the slot this lane's ray leaves and cannot accept (own_sphere), kOwnNone for none
 template <int W, bool REL>
 __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_t count, const RayPk &ray,
-                                             uint64_t (&wave)[kClWords], const ClConst &k, PfStats *ps) {
+                                             uint64_t (&wave)[kClWords], const ClConst &k, uint32_t own, PfStats *ps) {
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
     if (ps) ps->groups += count;
     // (the end offset opaque to the optimiser: it otherwise derives a trip count and runs a
@@ -506,14 +534,21 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
         if constexpr (W == 1) {
             const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
             const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
+            // (scene-wide tables: row 3 zw = the members' sphere slots, against the slot each lane leaves)
             if constexpr (kBehind)
-                merge_word1(wave[0], n0m, __builtin_amdgcn_ballot_w64(!(T.x < b0)), w0, n1m,
-                            __builtin_amdgcn_ballot_w64(!(T.y < b1)), w1);
+                merge_word1(wave[0], n0m, __builtin_amdgcn_ballot_w64(!(T.x < b0)),
+                            __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.z)), w0, n1m,
+                            __builtin_amdgcn_ballot_w64(!(T.y < b1)),
+                            __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.w)), w1);
             else
                 merge_word1(wave[0], n0m, w0, n1m, w1);
         } else {
-            const uint64_t f0m = kBehind ? n0m & __builtin_amdgcn_ballot_w64(!(T.x < b0)) : n0m;
-            const uint64_t f1m = kBehind ? n1m & __builtin_amdgcn_ballot_w64(!(T.y < b1)) : n1m;
+            const uint64_t f0m = kBehind ? n0m & __builtin_amdgcn_ballot_w64(!(T.x < b0)) &
+                                               __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.z))
+                                         : n0m;
+            const uint64_t f1m = kBehind ? n1m & __builtin_amdgcn_ballot_w64(!(T.y < b1)) &
+                                               __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.w))
+                                         : n1m;
             if constexpr (W == 2) {
                 uint64_t bw0[W], bw1[W];  // member 0 and 1 bits in word w
 #pragma unroll
@@ -588,7 +623,7 @@ __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const 
 // its sub-clusters' members too.
 template <bool SIMD, int W, bool GS, bool REL>
 __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray,
-                                                 Hit &h, bool fast, PfStats *ps) {
+                                                 Hit &h, bool fast, uint32_t own, PfStats *ps) {
     cv4f_t *ct = (cv4f_t *)a.clusters;
     uint64_t wave[kClWords] = {0ull, 0ull, 0ull, 0ull};
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
@@ -605,8 +640,8 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
     // the member pairs of an entered (sub-)cluster pair entry
     auto members = [&](v4f_t r2, bool in0, bool in1) {
         if (ps) ps->lane_pairs += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
-        if (in0) member_pairs<W, REL>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, wave, k, ps);
-        if (in1) member_pairs<W, REL>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, wave, k, ps);
+        if (in0) member_pairs<W, REL>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, wave, k, own, ps);
+        if (in1) member_pairs<W, REL>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, wave, k, own, ps);
     };
     // the sub-cluster pair entries [first, first + count) of an entered top cluster
     auto subs = [&](uint32_t first, uint32_t count) {
