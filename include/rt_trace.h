@@ -646,6 +646,18 @@ int rt_scene_groups(const rt_scene *scene, uint32_t enable_simd, float *out, uin
  * against it on the CPU (tests/test_prefilter_bound.py). */
 int rt_scene_clusters(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
                       uint32_t *out_f4, uint32_t *out_cpairs);
+/* The expanded form of a scene-wide table (test/inspection hook; DESIGN.md §3, "the expanded
+ * prefilter"): the same entries in the same layout, with centres S' = RN(S - c0), near-line
+ * thresholds t' = t - |S'|^2 + G and behind thresholds lowered by the error of the expanded T; mask
+ * rows, ranges and slots are those of rt_scene_clusters.  A lane with O' = RN(O - c0) skips on
+ *   fma(-T, T, A) >= t',  T = fma(S'x, Dx, fma(S'y, Dy, fma(S'z, Dz, -O'.D))),
+ *                         A = fma(S'x, -2O'x, fma(S'y, -2O'y, fma(S'z, -2O'z, |O'|^2))),
+ * and on T < b'.  *out_f4 = float4 rows (0: the scene has no scene-wide table), out_c0 = c0 (3 floats),
+ * *out_in_use = 1 where the table is proven and useful for the scene, so that the walk-specialised
+ * kernels run on it; 0: every launch walks the rt_scene_clusters table with the run-time kernel
+ * (rt_trace_info.Walk = 0).  out may be NULL to query the size. */
+int rt_scene_clusters_expanded(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
+                               uint32_t *out_f4, float *out_c0, uint32_t *out_in_use);
 /* The table's levels (test/inspection hook): *out_levels = 1 (cluster-pair
  * entries index member entries), 2 (tables of two or more pair-mask words: the
  * *out_cpairs top entries index *out_sub_pairs sub-cluster pair entries, which

@@ -212,6 +212,8 @@ SIGNATURES = {
     "rt_scene_clusters": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32),
                                   POINTER(c_uint32)]),
     "rt_scene_groups": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32), c_void_p]),
+    "rt_scene_clusters_expanded": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32),
+                                           POINTER(ctypes.c_float), POINTER(c_uint32)]),
     "rt_scene_cluster_layout": (c_int, [POINTER(RtScene), c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
     "rt_last_error": (c_char_p, []),
     "rt_on_init": (c_int, [POINTER(RtInitParams)]),
@@ -431,6 +433,21 @@ def scene_clusters(scene: RtScene, simd: bool = True):
     relative = bool(scene_prefilter(scene, simd)[2] & 4)
     rows = (5 if relative else 4) if words == 1 else 3 + words
     return tab.reshape(-1, rows, 4), int(ncp.value)
+
+
+def scene_clusters_expanded(scene: RtScene, simd: bool = True):
+    """The expanded form of a scene-wide cluster table (rt_scene_clusters_expanded): (table shaped as
+    scene_clusters' -- empty without one --, c0 (3,) f32, in_use)."""
+    nf4, use = c_uint32(), c_uint32()
+    c0 = (ctypes.c_float * 3)()
+    _check(lib().rt_scene_clusters_expanded(ctypes.byref(scene), int(simd), None, 0, ctypes.byref(nf4), c0,
+                                            ctypes.byref(use)), "rt_scene_clusters_expanded")
+    tab = np.zeros((nf4.value, 4), np.float32)
+    if nf4.value:
+        _check(lib().rt_scene_clusters_expanded(ctypes.byref(scene), int(simd), tab.ctypes.data, nf4.value,
+                                                ctypes.byref(nf4), c0, ctypes.byref(use)), "rt_scene_clusters_expanded")
+    rows = scene_clusters(scene, simd)[0].shape[1]
+    return tab.reshape(-1, rows, 4), np.array(list(c0), np.float32), bool(use.value)
 
 
 def scene_cluster_layout(scene: RtScene, simd: bool = True):

@@ -51,6 +51,9 @@ struct rt_device {
     float4 *d_clusters[2] = {nullptr, nullptr};  // clustered prefilter tables (cluster_table)
     size_t cap_clusters[2] = {0, 0};             // float4 capacity
     uint32_t n_cpairs[2] = {0, 0};               // 0: per-group prefilter loop
+    float4 *d_clusters_x[2] = {nullptr, nullptr};  // the expanded tables, {c0, 0} then the entries (cluster_table)
+    size_t cap_clusters_x[2] = {0, 0};             // float4 capacity
+    bool clusters_x_ok[2] = {false, false};        // proven and useful for the uploaded scene (kPrefilterExpanded)
     uint32_t cl_words[2] = {0, 0};
     // options Clusters off (0): per-group prefilter loop only; on (2): clustered loop up to
     // kClMaxGroups groups; default 1: up to kClAutoGroups (measured: clusters
@@ -329,6 +332,7 @@ extern "C" int rt_device_destroy(rt_device *d) {
         (void)hipFree(d->d_prim[r]);
         (void)hipFree(d->d_mats[r]);
         (void)hipFree(d->d_clusters[r]);
+        (void)hipFree(d->d_clusters_x[r]);
     }
     (void)hipFree(d->d_lut);
     (void)hipFree(d->d_weights);
@@ -576,12 +580,56 @@ static bool prefilter_rows(std::vector<float> &gv, uint32_t n_groups, bool simd)
 // involved -- a dropped lane runs no candidate for j unless another lane flags the pair, and then its
 // exact test reproduces this rejection.  tests/test_own_sphere_skip.py checks the claim on rays formed
 // as the reference forms them.
+//
+// Expanded (scene-wide tables; rtk_walk.h pair_prefilter_x, the walk-specialised kernels).  A second table
+// *xtab of the same entries, in front of it one row {c0, 0}: c0 = the midpoint of the bounding box of all
+// entry centres (cluster and member; f32).  Centres are S' = RN(S - c0), the kernel forms O' = RN(O - c0),
+//   T^ = fma(S'x, Dx, fma(S'y, Dy, fma(S'z, Dz, p))),          p = -RN-chain(O'.D)
+//   A^ = fma(S'x, -2O'x, fma(S'y, -2O'y, fma(S'z, -2O'z, oo))), oo = RN-chain(|O'|^2)
+//   e' = fma(-T^, T^, A^)
+// and skips on e' >= t' = RN+(t - |S'|^2 + G), t the entry's threshold above; behind on T^ < b' = b - H.
+// Mask rows, ranges, slots and rho are copied.  Bounds: a = max |S'| over the entries, b >= |O'| over every
+// origin (each lies on a scene sphere: sqrt(bound_m(c0)), the slack of M included), R = a + b, m = sqrt(M) of
+// the entry (M_j or M_c above: |C| <= m), C^ = S' - O' as a real vector.  Roundings (u each, |D| <= 1 + K/2):
+//  - S' and O': |C^ - (S - O)| <= u (|S'| + |O'|) <= u R, so |C^ - C_r| <= 1.01u (R + m) =: d for the
+//    reference's C_r = RN(S - O), and |C^| <= m (1 + 1e-3) inside M's own slack (R <= 10m where the table is used, below);
+//  - the chains: p and oo carry three roundings of partial sums <= |O'||D| and |O'|^2: 3.01u b|D|, 3.01u b^2;
+//    T^ adds three of partial sums <= (a + b)|D|:  |T^ - C^.D| <= 3.01u (a + 2b)|D| =: eT;
+//    A^ adds three of partial sums <= b^2 + 2ab:    |A^ - (|C^|^2 - |S'|^2)| <= u (6.02 b^2 + 6.02 ab);
+//  - the product T^2 is exact inside the last FMA, whose one rounding is of |A^ - T^2| <= max(a, m)^2 (1.01):
+//    u 1.01 max(a, m)^2;  and |T^2 - (C^.D)^2| <= eT (2|C^||D| + eT) <= 6.1u (a + 2b) m.
+//   Hence e' + |S'|^2 is within  u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m)  of f(C^) = |C^|^2 - (C^.D)^2.
+//  - f(C^) - l(O + C^) = (C^.D)^2 (1 - 1/|D|^2), at most K|C^|^2 <= K M (1 + 2.1e-3) in size;
+//  - member j: sqrt(l(O + C_r)) >= sqrt(l(O + C^)) - d, i.e. l(O + C_r) >= l(O + C^) - 2 d m - d^2, and the
+//    reference's dist_j >= l(O + C_r) - 13.3u M_j as above: the M-only terms (K (1 + 2.1e-3) + 13.3u + 2.02u) M_j
+//    (K + 15.9u) stay inside E_j = M_j (32u + 1.01K), which t already holds, and what is left is
+//      G >= u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m + 2.02 R m) + d^2;
+//  - cluster c: the proof above needs sqrt(l(q_c)) >= rho_c - u sqrt(M_c); now the point moves by u R 1.01, so
+//    it needs l(O + Q^) >= (rho_c + 1.01u R)^2, and rho_c <= 1.01 m: 2.05u R m more, M-only terms K M_c (1 + 2.1e-3).
+//  G = 1.25 u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m + 2.1 R m) per entry covers both (the head-room
+//  of 32u over the 23.5u derived above; d^2 <= 1.1 u^2 (R + m)^2 vanishes in it).  t' is rounded up after
+//  t - |S'|^2 + G is formed in f64 (|S'|^2 exact to 2^-52); t itself was rounded up.
+//  - behind: T^ is within eT + u R |D| <= u (4.02a + 7.03b)(1 + K) of (S - O).D where the proofs above allowed
+//    the prefilter's T 4u sqrt(M)|D|; H = u (4.5a + 7.5b) lowers every b by the whole new error (the old
+//    allowance is kept as slack), rounded down.
+// *x_ok (the launch fact "proven and useful", rt_kernel.h kPrefilterExpanded): every value of the table is
+// finite; G <= E/4 for every entry, E = M (32u + 1.01K) the slack already in t -- so the expanded form flags
+// at most what a threshold 1.25 E would, and R <= 10m as used above; and the scene lies near the origin of
+// its own coordinates.  The last is the premise's own margin: recentring makes G itself independent of where
+// the scene lies, but "every origin lies on a scene sphere" holds for an f32 origin only to its rounding,
+// (sqrt(3)/2) ulp(L) with L = max_i (|s_i|_inf + r_i), which M's slack (1e-3 + 1e-3 reach) was sized to absorb
+// for scenes near the origin and which the step |C^| <= m (1 + 1e-3) above draws on once more.  The expanded
+// table is used only where that rounding is below 1e-4, a tenth of the slack's absolute part (L < 1024);
+// a scene placed far from its own extent's scale keeps the plain table and the run-time kernel.
 // k_override / sub_override: rt_device_options ClusterCount / SubClusterSpheres (0: per scene, below).
 constexpr float kOwnR2Min = 2.6e-6f, kOwnR2Max = 256.0f;  // r in [16.1 eps, 16]
 static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, std::vector<float> &tab,
                               uint32_t *words, bool relative = false, uint32_t *levels = nullptr,
                               uint32_t *sub_pairs = nullptr, uint32_t k_override = 0, uint32_t sub_override = 0,
-                              std::vector<float> *own_rho = nullptr) {
+                              std::vector<float> *own_rho = nullptr, std::vector<float> *xtab = nullptr,
+                              bool *x_ok = nullptr) {
+    if (xtab) xtab->clear();
+    if (x_ok) *x_ok = false;
     if (levels) *levels = 0;
     if (sub_pairs) *sub_pairs = 0;
     if (own_rho) own_rho->assign(4u * (size_t)n_groups, INFINITY);
@@ -928,6 +976,60 @@ static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, s
             const float r2 = gv[(o.s / 4u) * 4u * kGroupF4 + 4u * kRowR2 + o.s % 4u];
             if (r2 >= kOwnR2Min && r2 <= kOwnR2Max) (*own_rho)[o.s] = r2;
         }
+    // the expanded table (proof above, "Expanded"): every entry half with a finite threshold is a real
+    // cluster or member; padding halves keep centre 0 and -inf (never entered, never flagged)
+    if (xtab && x_ok && !relative) {
+        const uint32_t n_ent = n_cp + n_sp + n_mp;
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint32_t e = 0; e < n_ent; ++e)
+            for (uint32_t w = 0; w < 2u; ++w) {
+                const float *en = &tab[(size_t)e * ef];
+                if (!std::isfinite(en[6 + w])) continue;
+                for (uint32_t ax = 0; ax < 3u; ++ax) {
+                    lo[ax] = std::min(lo[ax], (double)en[2u * ax + w]);
+                    hi[ax] = std::max(hi[ax], (double)en[2u * ax + w]);
+                }
+            }
+        const float c0[3] = {(float)(0.5 * (lo[0] + hi[0])), (float)(0.5 * (lo[1] + hi[1])), (float)(0.5 * (lo[2] + hi[2]))};
+        xtab->assign(4u + tab.size(), 0.0f);
+        float *xt = xtab->data() + 4u;
+        memcpy(xt, tab.data(), tab.size() * sizeof(float));
+        for (int ax = 0; ax < 3; ++ax) (*xtab)[(size_t)ax] = c0[ax];
+        double ra = 0.0;  // a = max |S'|
+        for (uint32_t e = 0; e < n_ent; ++e)
+            for (uint32_t w = 0; w < 2u; ++w) {
+                float *en = xt + (size_t)e * ef;
+                if (!std::isfinite(en[6 + w])) continue;
+                double ss = 0.0;
+                for (uint32_t ax = 0; ax < 3u; ++ax) {
+                    en[2u * ax + w] = (float)((double)en[2u * ax + w] - (double)c0[ax]);  // S' = RN(S - c0)
+                    ss += (double)en[2u * ax + w] * en[2u * ax + w];
+                }
+                ra = std::max(ra, std::sqrt(ss));
+            }
+        const double rb = std::sqrt(bound_m(c0[0], c0[1], c0[2])) * (1.0 + 1e-6);  // b >= |O'|
+        double place = 0.0;  // L = the largest coordinate an origin can have
+        for (const Sph &o : sp) place = std::max(place, std::max(std::fabs(o.x), std::max(std::fabs(o.y), std::fabs(o.z))) + o.r);
+        const float place_f = (float)place;
+        const double origin_rounding = 0.8661 * ((double)std::nextafter(place_f, INFINITY) - (double)place_f);
+        bool ok = std::isfinite(ra) && std::isfinite(rb) && origin_rounding <= 1e-4;
+        for (uint32_t e = 0; e < n_ent; ++e)
+            for (uint32_t w = 0; w < 2u; ++w) {
+                const float *src = &tab[(size_t)e * ef];
+                float *en = xt + (size_t)e * ef;
+                if (!std::isfinite(src[6 + w])) continue;
+                const double mm = bound_m(src[0 + w], src[2 + w], src[4 + w]), m = std::sqrt(mm);
+                const double am = std::max(ra, m);
+                const double g = 1.25 * u * (6.02 * rb * rb + 6.02 * ra * rb + 1.01 * am * am + 6.1 * (ra + 2.0 * rb) * m +
+                                             2.1 * (ra + rb) * m);
+                const double ss = (double)en[0 + w] * en[0 + w] + (double)en[2 + w] * en[2 + w] + (double)en[4 + w] * en[4 + w];
+                en[6 + w] = std::nextafter((float)((double)src[6 + w] - ss + g), INFINITY);
+                en[12 + w] = std::nextafter((float)((double)src[12 + w] - u * (4.5 * ra + 7.5 * rb)), -INFINITY);
+                ok = ok && g <= 0.25 * mm * (32.0 * u + 1.01 * K) && std::isfinite(en[0 + w]) && std::isfinite(en[2 + w]) &&
+                     std::isfinite(en[4 + w]) && std::isfinite(en[6 + w]) && std::isfinite(en[12 + w]);
+            }
+        *x_ok = ok && std::isfinite(c0[0]) && std::isfinite(c0[1]) && std::isfinite(c0[2]);
+    }
     if (levels) *levels = two ? 2u : 1u;
     if (sub_pairs) *sub_pairs = n_sp;
     return n_cp;
@@ -960,6 +1062,10 @@ struct PackedSet {
     uint32_t n_cpairs = 0, cl_words = 0;
     uint32_t cl_levels = 0, cl_sub_pairs = 0;  // two-level tables (cl_words >= 2)
     std::vector<float> own_rho;  // per slot: word 3 of the sphere record's centre row (cluster_table, "own sphere")
+    // the expanded table of a scene-wide table (cluster_table, "expanded"): the row {c0, 0}, then the entries;
+    // empty without one.  clusters_x_ok: proven and useful (the launch fact kPrefilterExpanded)
+    std::vector<float> clusters_x;
+    bool clusters_x_ok = false;
 };
 
 static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env = -1, uint32_t cluster_k = 0,
@@ -1017,7 +1123,11 @@ static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env 
     // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
     p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
     p.n_cpairs = cluster_table(gv, n, p.clusters, &p.cl_words, p.relative, &p.cl_levels, &p.cl_sub_pairs, cluster_k,
-                               sub_spheres, &p.own_rho);
+                               sub_spheres, &p.own_rho, &p.clusters_x, &p.clusters_x_ok);
+    if (!p.n_cpairs) {
+        p.clusters_x.clear();
+        p.clusters_x_ok = false;
+    }
     // (a record per real sphere of the scalar set, per slot of the SIMD set; without a table every rho is +inf)
     for (uint32_t sl = 0; sl < (rs == 0 ? 4u * n : ns); ++sl) p.mats[(size_t)sl * 4u * kSphereF4 + 3u] = p.own_rho[sl];
     if (p.relative)
@@ -1061,6 +1171,22 @@ extern "C" int rt_scene_upload(rt_device *d, const rt_scene *scene) {
                                   d->stream));
             d->n_cpairs[rs] = ps[rs].n_cpairs;
             d->cl_words[rs] = ps[rs].cl_words;
+        }
+        const size_t xf4 = ps[rs].clusters_x.size() / 4u;
+        d->clusters_x_ok[rs] = false;
+        if (xf4 > d->cap_clusters_x[rs]) {
+            HIP_OK(hipStreamSynchronize(d->stream));
+            (void)hipFree(d->d_clusters_x[rs]);
+            d->d_clusters_x[rs] = nullptr;
+            d->cap_clusters_x[rs] = 0;
+            if (hipMalloc(&d->d_clusters_x[rs], xf4 * 16u) != hipSuccess)
+                return fail(RT_ENOMEM, "rt_scene_upload: device allocation failed");
+            d->cap_clusters_x[rs] = xf4;
+        }
+        if (xf4 && nf4) {
+            HIP_OK(hipMemcpyAsync(d->d_clusters_x[rs], ps[rs].clusters_x.data(), xf4 * 16u, hipMemcpyHostToDevice,
+                                  d->stream));
+            d->clusters_x_ok[rs] = ps[rs].clusters_x_ok;
         }
     }
     HIP_OK(hipStreamSynchronize(d->stream));
@@ -1142,6 +1268,23 @@ extern "C" int rt_scene_clusters(const rt_scene *scene, uint32_t enable_simd, fl
     if (out) {
         if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_clusters: capacity %u < %u", capacity_f4, nf4);
         memcpy(out, p.clusters.data(), (size_t)nf4 * 16u);
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_clusters_expanded(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
+                                          uint32_t *out_f4, float *out_c0, uint32_t *out_in_use) {
+    if (!scene || !out_f4 || !out_c0 || !out_in_use) return fail(RT_EINVAL, "rt_scene_clusters_expanded: NULL argument");
+    PackedSet p;
+    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
+    if (rc) return rc;
+    const uint32_t nf4 = p.clusters_x.empty() ? 0u : (uint32_t)(p.clusters_x.size() / 4u) - 1u;
+    *out_f4 = nf4;
+    *out_in_use = p.clusters_x_ok ? 1u : 0u;
+    for (int ax = 0; ax < 3; ++ax) out_c0[ax] = nf4 ? p.clusters_x[(size_t)ax] : 0.0f;
+    if (out) {
+        if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_clusters_expanded: capacity %u < %u", capacity_f4, nf4);
+        if (nf4) memcpy(out, p.clusters_x.data() + 4u, (size_t)nf4 * 16u);
     }
     return RT_OK;
 }
@@ -1529,6 +1672,20 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
         // the walk-specialised kernel this launch asks for, or the run-time one (rt_kernel.h, the routing
         // rule: a.clusters is set only with n_cpairs >= 1, above, and Frames == 0 returned above)
         a.walk = rtk_walk_request(a, d->walk_any_env != 0);
+        // The expanded table goes to the kernels that hold the expanded prefilter, and to no other (rt_kernel.h
+        // kPrefilterExpanded): offered here, and taken back unless this launch's kernel is one of them.
+        if (a.clusters && !a.pf_relative && d->clusters_x_ok[rs] && !d->walk_any_env) {
+            const float4 *plain = a.clusters;
+            a.clusters = d->d_clusters_x[rs];  // (the row {c0, 0}, then entry 0)
+            a.prefilter = kPrefilterExpanded;
+            a.walk = rtk_walk_request(a, false);
+            if (!rtk_walk_expanded(a, d->cull != 0, lpp)) {
+                // (a shape or a device without walk kernels: the request stands, as it always did for such a
+                // launch, and rtk_walk_kernel gives it the run-time kernel, now for want of the expanded table too)
+                a.clusters = plain;
+                a.prefilter = kPrefilterOn;
+            }
+        }
     }
     const int src = a.scene_in_lds ? d->src : kSrcSmem;  // a scene in HBM is read through the scalar cache
     if (counts && !a.solo && !rtk_tile_counts_four_wave(a.scene_in_lds, src)) {

@@ -70,7 +70,7 @@ struct TraceArgs {
     uint32_t n_groups, n_spheres, use_sky, flags;  // n_spheres: scalar rule set only
     uint32_t band_rows, band_count, band_index;
     uint32_t sec_threshold;      // lanes that must wait for a secondary iteration
-    uint32_t prefilter;          // secondary sphere loop: FMA prefilter + exact recheck (r2p valid)
+    uint32_t prefilter;          // secondary sphere loop: FMA prefilter + exact recheck (r2p valid); kPrefilter*
     uint32_t fast_sqrt;          // every hittable r^2 is 0 or in [2^-36, 2^60] (candidate sqrt_rn)
     unsigned long long *stats;   // optional (RT_STATS): kStat* counters, NULL = off
     unsigned long long *wave_times;  // optional (RT_WAVETIMES): per-wave {start, end} s_memrealtime
@@ -167,6 +167,12 @@ constexpr uint32_t kMergeGroups = 2;
 constexpr uint32_t kCullCounterWords = 132;
 constexpr uint32_t kCullTotals = 128;
 constexpr uint32_t kCullFolded = 130;  // a per-tile launch's folded segments (rtk_launch_empty_counts), per launch
+// TraceArgs.prefilter: off, on, or on with `clusters` naming the expanded table -- the scene-wide
+// table recentred on c0, `clusters` naming the float4 row {c0, 0} and entry 0 the row behind it, its thresholds those of the
+// 7-op estimate (rtk_walk.h pair_prefilter_x; rt_host.cpp cluster_table, "expanded").  The host sets
+// the last only where that table exists and is proven and useful for the scene, and only for a
+// launch of a kernel that reads it (below); every other kernel tests the field as a boolean.
+enum { kPrefilterOff = 0, kPrefilterOn = 1, kPrefilterExpanded = 2 };
 // Secondary-ray walk variants (rtk_shape.h Walk<>): any (run-time dispatch),
 // the per-group loops, or a cluster walk with 1/2/4 pair-mask words and
 // scene-wide or per-lane ("Rel") thresholds
@@ -194,6 +200,12 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 //   cluster walks   run only with a non-empty table over a non-empty scene: clusters set,
 //                   n_cpairs >= 1, n_groups >= 1 (their top loop has no zero-trip test), and with the
 //                   prefilter on (they do not test it; rt_trace sets clusters only with it)
+//   expanded table  the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4) hold the expanded prefilter alone:
+//                   they run only where `clusters` is the expanded table (prefilter == kPrefilterExpanded:
+//                   it exists, every value of it is finite, and its extra slack G stays within a quarter
+//                   of each entry's own E -- rt_host.cpp cluster_table).  A scene-wide table without that
+//                   (a scene placed far from its own extent's scale) is walked by the run-time kernel
+//                   on the table as it always was.
 // and the kernels exist only for the culled production shapes (rtk_walk_shape).  Every other launch
 // runs the run-time kernel (kWalkAny), which tests each fact where it matters and dispatches the
 // walk the table asks for.
@@ -202,6 +214,7 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 static inline uint32_t rtk_walk_request(const TraceArgs &a, bool walk_any) {
     if (walk_any || !a.fast_sqrt || a.max_bounce == 0u) return kWalkAny;
     if (!a.clusters) return kWalkGroups;
+    if (!a.pf_relative && a.prefilter != (uint32_t)kPrefilterExpanded) return kWalkAny;
     if (a.cl_words == 1u) return a.pf_relative ? kWalkCl1Rel : kWalkCl1;
     if (a.cl_words == 2u) return a.pf_relative ? kWalkCl2Rel : kWalkCl2;
     return a.pf_relative ? kWalkCl4Rel : kWalkCl4;
@@ -217,7 +230,16 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
     if (!a.fast_sqrt || a.max_bounce == 0u || a.frames == 0u) return kWalkAny;
     if (a.walk >= (uint32_t)kWalkCl1 && (a.clusters == nullptr || a.n_cpairs == 0u || a.n_groups == 0u || !a.prefilter))
         return kWalkAny;
+    if (a.walk >= (uint32_t)kWalkCl1 && a.walk <= (uint32_t)kWalkCl4 && a.prefilter != (uint32_t)kPrefilterExpanded)
+        return kWalkAny;
+    // (and the expanded table is read by no other kernel: the host decides with rtk_walk_expanded)
     return a.walk <= (uint32_t)kWalkCl4Rel ? a.walk : (uint32_t)kWalkAny;
+}
+// Whether the launch's kernel walks the expanded table: rt_trace offers it (clusters = the expanded
+// table, prefilter = kPrefilterExpanded), asks this, and puts the plain table back where the answer is no.
+static inline bool rtk_walk_expanded(const TraceArgs &a, int cull, int lanes_per_pixel) {
+    const uint32_t k = rtk_walk_kernel(a, cull, lanes_per_pixel);
+    return k >= (uint32_t)kWalkCl1 && k <= (uint32_t)kWalkCl4;
 }
 
 enum { kStatPriIters = 0, kStatPriLanes, kStatSecIters, kStatSecLanes, kStatPriGroups, kStatSecHitGroups,

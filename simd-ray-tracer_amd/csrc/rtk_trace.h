@@ -692,7 +692,9 @@ void trace_kernel(TraceArgs a) {
                         if (SRC == kSrcSmem && pf && (Walk<WALK>::CLUSTERS || a.n_cpairs)) {
                             PfStats *ps = st.pf_round();
                             if constexpr (Walk<WALK>::CLUSTERS) {
-                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL>(a, lds_groups, ray, h, fast, own, ps);
+                                // (the scene-wide walk kernels hold the expanded prefilter: rtk_walk.h pair_prefilter_x)
+                                clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL, !Walk<WALK>::REL>(a, lds_groups, ray, h, fast,
+                                                                                                            own, ps);
                             } else if constexpr (WALK == kWalkGroups) {
                                 __builtin_unreachable();  // the host runs kWalkGroups kernels without a cluster table
                             } else if (a.pf_relative) {

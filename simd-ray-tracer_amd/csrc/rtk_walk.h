@@ -178,6 +178,52 @@ __device__ __forceinline__ f2 pair_prefilter(const RayPk &r, f2 sx, f2 sy, f2 sz
     return e;
 }
 
+// The expanded prefilter of the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4; rt_host.cpp
+// cluster_table, "expanded", proves it): the same estimate written as dot products of the centre
+// itself, so the three packed subtractions C = S - O per pair go and nothing is left per sphere but
+// FMAs -- 7 packed ops instead of 10, the centre rows still in SGPRs.  With S' = RN(S - c0) from the
+// host's second table and O' = RN(O - c0) (c0: the table's centre, so that the values that cancel
+// stay of the scene's own size):
+//   T  = fma(S'x, Dx, fma(S'y, Dy, fma(S'z, Dz, -O'.D)))           ~ (S - O).D
+//   A  = fma(S'x, -2O'x, fma(S'y, -2O'y, fma(S'z, -2O'z, |O'|^2)))  ~ |S - O|^2 - |S'|^2
+//   e' = fma(-T, T, A)                                              ~ e - |S'|^2
+// and the table's thresholds are t' = t - |S'|^2 + G (near the line: e' >= t' skips) and behind
+// thresholds lowered by T's new error.  The ray's part, formed once per walk in this fixed order:
+//   O'    = O - c0 per axis (one rounding each)
+//   |O'|^2 = fma(O'x, O'x, fma(O'y, O'y, O'z O'z))
+//   -O'.D  = -fma(O'x, Dx, fma(O'y, Dy, O'z Dz))
+// held as three pairs {-2O', D} (the doubling and the negation are exact) and {|O'|^2, -O'.D}, so a
+// packed op broadcasts either half with op_sel as pair_prefilter does.
+struct RayX {
+    f2 x, y, z;  // {-2O', D} per axis
+    f2 w;        // {|O'|^2, -O'.D}
+};
+
+// Written where the walk starts (as walk_const): c0 is read from the table there and the origin passes
+// through an empty asm, so the block is neither formed at shading time nor held across the trip loop.
+__device__ __forceinline__ RayX ray_expand(const RayPk &r, v4f_t c0) {
+    float ox = r.x.x - c0.x, oy = r.y.x - c0.y, oz = r.z.x - c0.z;
+    asm volatile("" : "+v"(ox), "+v"(oy), "+v"(oz));
+    const float dx = r.x.y, dy = r.y.y, dz = r.z.y;
+    const float oo = __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz));
+    const float od = __builtin_fmaf(ox, dx, __builtin_fmaf(oy, dy, oz * dz));
+    return {f2{-2.0f * ox, dx}, f2{-2.0f * oy, dy}, f2{-2.0f * oz, dz}, f2{oo, -od}};
+}
+
+__device__ __forceinline__ f2 pair_prefilter_x(const RayX &r, f2 sx, f2 sy, f2 sz, f2 &T) {
+    f2 A, e;
+    asm("v_pk_fma_f32 %[T], %[sz], %[rz], %[rw] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[T], %[sy], %[ry], %[T] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[T], %[sx], %[rx], %[T] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %[A], %[sz], %[rz], %[rw] op_sel_hi:[1,0,0]\n\t"
+        "v_pk_fma_f32 %[A], %[sy], %[ry], %[A] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %[A], %[sx], %[rx], %[A] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %[e], %[T], %[T], %[A] neg_lo:[1,0,0] neg_hi:[1,0,0]"
+        : [T] "=&v"(T), [A] "=&v"(A), [e] "=&v"(e)
+        : [sx] "s"(sx), [sy] "s"(sy), [sz] "s"(sz), [rx] "v"(r.x), [ry] "v"(r.y), [rz] "v"(r.z), [rw] "v"(r.w));
+    return e;
+}
+
 // The exact recheck of one group's flagged sphere pairs (f01, f23): only such
 // a pair reruns the exact packed test (same ops as test_group) and the exact
 // candidate logic decides, so results are identical.
@@ -505,9 +551,11 @@ __device__ __forceinline__ uint32_t own_sphere(const Sample &p, float4 sc, uint3
 }
 
 // own (scene-wide tables): the slot this lane's ray leaves and cannot accept (own_sphere), kOwnNone for none
-template <int W, bool REL>
-__device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_t count, const RayPk &ray,
+// X: the expanded prefilter on the recentred table (pair_prefilter_x; scene-wide tables only)
+template <int W, bool REL, bool X>
+__device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_t count, const RayPk &ray, const RayX &rx,
                                              uint64_t (&wave)[kClWords], const ClConst &k, uint32_t own, PfStats *ps) {
+    static_assert(!(X && REL), "the expanded prefilter is for scene-wide tables");
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
     if (ps) ps->groups += count;
     // (the end offset opaque to the optimiser: it otherwise derives a trip count and runs a
@@ -518,8 +566,9 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
         cv4f_t *e = cl_entry(ct, off);
         const Rows4 rows = load_rows4(e);  // (one scalar load per entry)
         const v4f_t r0 = rows.r0, r1 = rows.r1, r2 = rows.r2, r3 = rows.r3;
-        f2 T, cc;
-        const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
+        f2 T, cc = {};
+        const f2 v = X ? pair_prefilter_x(rx, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T)
+                       : pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
         // a lane may hit the sphere: near the line, and not wholly behind the origin
         const f2 tr = REL ? member_thr(cc, k, f2{r1.z, r1.w}) : f2{r1.z, r1.w};
         const float t0 = tr.x, t1 = tr.y;
@@ -588,14 +637,15 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
 // margin E (a ground-plane scene: rays leaving the ground cross the thin layer
 // of small spheres only near their origin).
 // (The sub-level slab and behind tests stay: without them RTWeekend -0.1 % and -3 %, profiles/r06n_slab_ab.txt.)
-template <bool REL>
-__device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const ClConst &k, uint64_t &m0,
+template <bool REL, bool X>
+__device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const RayX &rx, const ClConst &k, uint64_t &m0,
                                              uint64_t &m1, v4f_t &ranges) {
     const Rows4 rows = load_rows4(e);  // (one scalar load per entry; row 2 = the entry's ranges)
     const v4f_t r0 = rows.r0, r1 = rows.r1, r3 = rows.r3;
     ranges = rows.r2;
-    f2 T, cc;
-    const f2 v = pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
+    f2 T, cc = {};
+    const f2 v = X ? pair_prefilter_x(rx, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T)
+                   : pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
     if constexpr (REL) {
         f2 t, b;
         cluster_thr(cc, k, f2{r1.z, r1.w}, f2{r3.x, r3.y}, t, b);
@@ -621,10 +671,15 @@ __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const 
 // whose ranges index the member entries (rt_host.cpp cluster_table); the bound
 // of a cluster covers every sphere under it, so a skipped top cluster skips
 // its sub-clusters' members too.
-template <bool SIMD, int W, bool GS, bool REL>
+// X: the walk-specialised scene-wide kernels' expanded prefilter (pair_prefilter_x): a.clusters is then
+// the recentred table, whose first row holds its centre c0, in front of entry 0 (rt_host.cpp cluster_table,
+// "expanded"; rt_kernel.h kPrefilterExpanded is the launch fact).
+template <bool SIMD, int W, bool GS, bool REL, bool X = false>
 __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray,
                                                  Hit &h, bool fast, uint32_t own, PfStats *ps) {
-    cv4f_t *ct = (cv4f_t *)a.clusters;
+    // (X: a.clusters names the row {c0, 0}, entry 0 the row behind it -- one more immediate offset of
+    // every entry's load, where a row in front of the table cost an address pair of its own)
+    cv4f_t *ct = (cv4f_t *)a.clusters + (X ? 1 : 0);
     uint64_t wave[kClWords] = {0ull, 0ull, 0ull, 0ull};
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
     constexpr bool kTwoLevels = W >= 2;
@@ -637,11 +692,13 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         k.kp = f2{walk_const(kPfRel), walk_const(kSlabRel)};
         k.aux = f2{slab_e0, __builtin_fabsf(dy)};
     }
+    RayX rx = {};
+    if constexpr (X) rx = ray_expand(ray, *(cv4f_t *)a.clusters);
     // the member pairs of an entered (sub-)cluster pair entry
     auto members = [&](v4f_t r2, bool in0, bool in1) {
         if (ps) ps->lane_pairs += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
-        if (in0) member_pairs<W, REL>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, wave, k, own, ps);
-        if (in1) member_pairs<W, REL>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, wave, k, own, ps);
+        if (in0) member_pairs<W, REL, X>(ct, __float_as_uint(r2.x), __float_as_uint(r2.y), ray, rx, wave, k, own, ps);
+        if (in1) member_pairs<W, REL, X>(ct, __float_as_uint(r2.z), __float_as_uint(r2.w), ray, rx, wave, k, own, ps);
     };
     // the sub-cluster pair entries [first, first + count) of an entered top cluster
     auto subs = [&](uint32_t first, uint32_t count) {
@@ -650,7 +707,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
             cv4f_t *e = cl_entry(ct, off);
             uint64_t m0, m1;
             v4f_t r2;
-            cluster_pair<REL>(e, ray, k, m0, m1, r2);
+            cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2);
             members(r2, m0 != 0, m1 != 0);
         }
     };
@@ -663,7 +720,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         cv4f_t *e = cl_entry(ct, off);
         uint64_t m0, m1;
         v4f_t r2;
-        cluster_pair<REL>(e, ray, k, m0, m1, r2);
+        cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2);
         if constexpr (kTwoLevels) {
             if (ps) ps->lane_pairs += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
             if (ps) ps->cl_top_entered += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
