@@ -14,7 +14,7 @@
  * success or a negative errno-style code (RT_E*).  Calls on one rt_device are
  * single-threaded; each device owns one HIP stream unless a stream is passed.
  * Structs marked "byte-compatible" have the reference's exact layout
- * (offsets asserted in simd-ray-tracer_amd/csrc/rt_host.cpp and tests/).
+ * (offsets asserted in simd-ray-tracer_amd/csrc/rt_scene.cpp and tests/).
  */
 #ifndef RT_TRACE_H
 #define RT_TRACE_H

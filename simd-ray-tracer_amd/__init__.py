@@ -425,7 +425,7 @@ def scene_clusters(scene: RtScene, simd: bool = True):
     if nf4.value:
         _check(lib().rt_scene_clusters(ctypes.byref(scene), int(simd), tab.ctypes.data, nf4.value, ctypes.byref(nf4),
                                        ctypes.byref(ncp)), "rt_scene_clusters")
-    # the pair-mask words follow the rule set's group count (rt_host.cpp pack_set):
+    # the pair-mask words follow the rule set's group count (rt_pack.cpp cluster_table):
     # SIMDSpheres groups for the SIMD rules, ceil(ScalarSpheres / 4) for the scalar ones;
     # per-lane ("relative") tables carry a fifth row at one word (the height slab)
     groups = scene.SIMDSpheres.Count if simd else (scene.ScalarSpheres.Count + 3) // 4

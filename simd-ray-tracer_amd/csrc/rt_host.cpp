@@ -7,10 +7,10 @@
 #include <string.h>
 
 #include <algorithm>
-#include <cmath>
 #include <vector>
 
 #include "rt_kernel.h"
+#include "rt_pack.h"
 #include "rt_trace.h"
 
 // Two pinned slots the library owns, from which words a launch reads on the device are uploaded.
@@ -48,10 +48,10 @@ struct rt_device {
     uint32_t pf_relative[2] = {0, 0};  // per rule set: the threshold row holds r^2, per-lane thresholds (rtk_walk.h kPfRel)
     int pf_rel_env = -1;  // options PrefilterRelative: -1 auto (where the scene-wide bound does not pay), 0 never, 1 always
     uint32_t fast_sqrt[2] = {0, 0};  // per rule set: candidate sqrt in sqrt_rn's verified range
-    float4 *d_clusters[2] = {nullptr, nullptr};  // clustered prefilter tables (cluster_table)
+    float4 *d_clusters[2] = {nullptr, nullptr};  // clustered prefilter tables (rt_pack.cpp cluster_table)
     size_t cap_clusters[2] = {0, 0};             // float4 capacity
     uint32_t n_cpairs[2] = {0, 0};               // 0: per-group prefilter loop
-    float4 *d_clusters_x[2] = {nullptr, nullptr};  // the expanded tables, {c0, 0} then the entries (cluster_table)
+    float4 *d_clusters_x[2] = {nullptr, nullptr};  // the expanded tables, {c0, 0} then the entries (rt_pack.cpp expand_table)
     size_t cap_clusters_x[2] = {0, 0};             // float4 capacity
     bool clusters_x_ok[2] = {false, false};        // proven and useful for the uploaded scene (kPrefilterExpanded)
     uint32_t cl_words[2] = {0, 0};
@@ -184,7 +184,7 @@ static int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-// rt_kernel.h: the error text other translation units (rt_multi.cpp) report
+// rt_pack.h: the error text other translation units (rt_pack.cpp, rt_multi.cpp) report
 int rt_fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -410,8 +410,7 @@ extern "C" int rt_set_rsqrt_table(rt_device *d, const float table[2048]) {
     return RT_OK;
 }
 
-// Packs one rule set: positions/radii as 4-wide groups with r*r precomputed,
-// sphere records as {centre.xyz, rho}, {Color.xyz, Specular}, {Emissive.xyz, IOR}, {0} (kSphereF4).
+// One packed rule set's group rows and sphere records (rt_pack.cpp pack_set; rt_layout.h) to the device.
 static int upload_set(rt_device *d, int rs, const std::vector<float> &groups, const std::vector<float> &mats,
                       uint32_t n_groups) {
     if (n_groups > d->cap_groups[rs]) {
@@ -437,704 +436,19 @@ static int upload_set(rt_device *d, int rs, const std::vector<float> &groups, co
     return RT_OK;
 }
 
-static void put_material(float *dst, const rt_material &m) {
-    dst[0] = m.Color.x;
-    dst[1] = m.Color.y;
-    dst[2] = m.Color.z;
-    dst[3] = m.Specular;
-    dst[4] = m.Emissive.x;
-    dst[5] = m.Emissive.y;
-    dst[6] = m.Emissive.z;
-    dst[7] = m.IndexOfRefraction;
-    // row 3: the dielectric path's per-material quotients, the reference's own f32 divisions done
-    // once here (IEEE, as the kernel's were): eta outside = 1/IOR (main.cpp:463) and Reflectance's
-    // r0 = ((1 - eta)/(1 + eta))^2 (main.cpp:292-295) for eta outside and inside (= IOR)
-    if (m.IndexOfRefraction != 0.0f) {
-        const float ior = m.IndexOfRefraction, eo = 1.0f / ior;
-        const float ro = (1.0f - eo) / (1.0f + eo), ri = (1.0f - ior) / (1.0f + ior);
-        dst[8] = eo;
-        dst[9] = ro * ro;
-        dst[10] = ri * ri;
+// A cluster table's device buffer grown to hold `tab` (the stream's copies into the old one wait first),
+// and the table, if there is one, copied into it on the device's stream.
+static int upload_table(rt_device *d, float4 *&buf, size_t &cap, const std::vector<float> &tab) {
+    const size_t nf4 = tab.size() / 4u;
+    if (nf4 > cap) {
+        HIP_OK(hipStreamSynchronize(d->stream));
+        (void)hipFree(buf);
+        buf = nullptr;
+        cap = 0;
+        if (hipMalloc(&buf, nf4 * 16u) != hipSuccess) return fail(RT_ENOMEM, "rt_scene_upload: device allocation failed");
+        cap = nf4;
     }
-}
-
-// Prefilter thresholds r2p (row 4 of each group) for the secondary-ray
-// sphere loop (rtk_walk.h, pair_prefilter).  Secondary origins are hit
-// points, i.e. lie within |r_i| of a hittable sphere centre s_i, so
-//   M_j = (max_i |s_i - s_j| + |r_i|)^2   (with slack for origin rounding)
-// bounds |C|^2 for sphere j, and r2p_j = r^2_j + M_j (32u + 1.01K) rounded
-// up (u = 2^-24, K = 2^-16) exceeds the prefilter's error bound.  Spheres
-// that can never pass the exact test (SIMD r^2 <= 0, scalar padding) get
-// -inf: never flagged.  Returns whether the prefilter pays for this scene
-// (thresholds not far above r^2 on average).
-static bool prefilter_rows(std::vector<float> &gv, uint32_t n_groups, bool simd) {
-    std::vector<uint32_t> hit;
-    for (uint32_t s = 0; s < 4u * n_groups; ++s) {
-        const float r2 = gv[(s / 4u) * 4u * kGroupF4 + 4u * kRowR2 + s % 4u];
-        if (simd ? r2 > 0.0f : r2 >= 0.0f) hit.push_back(s);
-    }
-    double ratio = 0.0;
-    uint32_t n_ratio = 0;
-    for (uint32_t j = 0; j < 4u * n_groups; ++j) {
-        const uint32_t gj = (j / 4u) * 4u * kGroupF4, lj = j % 4u;
-        const float r2 = gv[gj + 4u * kRowR2 + lj];
-        float &r2p = gv[gj + 4u * kRowR2P + lj];
-        if (!(simd ? r2 > 0.0f : r2 >= 0.0f) || !std::isfinite(r2)) {
-            r2p = -INFINITY;
-            continue;
-        }
-        double reach = 0.0;
-        for (uint32_t i : hit) {
-            const uint32_t gi = (i / 4u) * 4u * kGroupF4, li = i % 4u;
-            const double dx = (double)gv[gi + 4u * kRowX + li] - gv[gj + 4u * kRowX + lj],
-                         dy = (double)gv[gi + 4u * kRowY + li] - gv[gj + 4u * kRowY + lj],
-                         dz = (double)gv[gi + 4u * kRowZ + li] - gv[gj + 4u * kRowZ + lj];
-            const double ri = std::sqrt((double)gv[gi + 4u * kRowR2 + li]);
-            reach = std::max(reach, std::sqrt(dx * dx + dy * dy + dz * dz) + ri);
-        }
-        const double m = (reach * 1.001 + 1e-3) * (reach * 1.001 + 1e-3);
-        const double e = m * (32.0 * 0x1p-24 + 1.01 * 0x1p-16);
-        r2p = std::nextafter((float)((double)r2 + e), INFINITY);
-        ratio += std::min(e / std::max((double)r2, 1e-30), 10.0);
-        n_ratio += 1;
-    }
-    return n_ratio > 0 && ratio / n_ratio < 0.5;
-}
-
-// Clustered prefilter table (rt_kernel.h, cl_entry_f4(words) rows per entry) for the
-// secondary-ray sphere loop: the hittable spheres are grouped into about
-// sqrt(n) spatial clusters (deterministic k-means; any membership -- the
-// exact test still runs in the reference's group order).  A cluster c with
-// centre q_c is skipped by a wave when every lane's FMA estimate
-// e_c = |Q|^2 - (Q.D)^2, Q = RN(q_c - O), satisfies e_c >= rc2p_c.  Proof
-// that skipping is exact (u = 2^-24, K = 2^-16, l(p) = the exact squared
-// distance from point p to the ray's line; distance to a line is 1-Lipschitz):
-//  - e_c is within M_c (10.2u + K(1+K)/(1-K)) of l(O + Q) (as for spheres,
-//    plus the 1/|D|^2 factor of l), M_c a bound on |Q|^2 over every secondary
-//    origin; so e_c >= rc2p_c = rho_c^2 + M_c (32u + 1.01K) gives
-//    l(O + Q) >= rho_c^2, and |Q - (q_c - O)| <= u sqrt(M_c) moves the point
-//    by at most that: sqrt(l(q_c)) >= rho_c - u sqrt(M_c);
-//  - member j: sqrt(l(s_j)) >= sqrt(l(q_c)) - |s_j - q_c|, and the
-//    reference's rounded C_j moves s_j by <= u sqrt(M_j) again;
-//  - the reference-rounded dist_j (exact ops on C_j: >= l(O + C_j)) is within
-//    13.3u M_j of its exact value, so l(O + C_j) > sigma_j^2 = r_j^2 + 13.3u M_j
-//    makes dist_j > r_j^2: a miss under both rule sets.
-// Hence rho_c = max_j (|s_j - q_c| + sigma_j + u sqrt(M_j)) + u sqrt(M_c),
-// inflated by 1e-6 relative.  Members of a passing cluster are tested with
-// their own r2p (the per-sphere bound above); a sphere pair some lane may
-// hit sets its bit in the wave's pair mask, and the exact recheck walks that
-// mask in group order.  Returns the number of cluster-pair entries (0: not
-// used -- more than kClMaxGroups groups, too few hittable spheres); *words =
-// u64 words of the pair mask.
-//
-// relative (the per-lane thresholds of pack_set, where the scene-wide M makes
-// the bound above useless): the thresholds are formed per lane from the lane's
-// own cc = |Q|^2 (rtk_walk.h kClRel / kPfRel / kBehindRel).  With A_j =
-// |Q|(1+u) + delta_j >= |C_j| (delta_j = |s_j - q_c|) the chain above reads
-//   sqrt(l(O+Q)) > delta_j + sqrt(r_j^2 + 13.3u A_j^2) + 2u A_j + u|Q|
-// and sqrt(r^2 + 13.3u A^2) <= r + sqrt(13.3u) A, so it holds when
-//   sqrt(l(O+Q)) > rho_j + a|Q|,  rho_j = delta_j (1+s) + r_j,  s = sqrt(13.3u) + 2u,  a = s(1+u) + u;
-// (rho + a|Q|)^2 <= rho^2 (1+a) + |Q|^2 (a + a^2), l(O+Q) >= e_c - E1 |Q|^2
-// (E1 = 10.2u + K(1+K)/(1-K)) and |Q|^2 <= cc (1 + 5.1u), so the cluster is
-// skipped when e_c >= RN(cc kClRel + R_c), R_c = rho_c^2 (1+a) rounded up,
-// kClRel >= (a + a^2 + E1)(1 + 6u) (both inflated for the FMA's rounding).
-// Members carry r^2 (the group rows' per-lane rule), behind thresholds lose
-// their M terms (|Q|, |C_j| <= (1 + cc)/2 bound them per lane, kBehindRel):
-//   cluster  -(max_j ((delta_j + r_j)(1 + 2^-15) + 4.3u delta_j) + 4.3u),
-//   member   -(r_j (1 + 2^-15) + 4.3u),
-// and a lane's behind test is T < RN(stored - 4.5u cc).
-//
-// Own sphere (scene-wide tables; rtk_walk.h own_sphere).  A lane that continues a path from sphere j
-// (slot j: word 2 / 3 of row 3 of j's member entry) leaves j out of its own member flags when
-//   |d| < RN(-T lambda),   d = RN(rho_j - cc kappa),   kappa = 1 - 320u,  lambda = 1.9 eps,
-// with C = RN(S_j - O) per axis -- the reference's own C_j, bit for bit -- and the FMA values
-// cc ~ |C|^2, T ~ C.D of pair_prefilter; rho_j = r_j^2 (the f32 the exact test compares with; word 3
-// of the record's centre row) for the table's members with r_j^2 in [kOwnR2Min, kOwnR2Max], else +inf
-// (d = +inf or NaN: never).  Everything below is a function of C, D and r_j^2 alone, so nothing is
-// assumed about the segment that led to O (its length, its direction's norm, which root was taken, how
-// O was rounded): the test measures how far O lies off the sphere instead of bounding it.
-// Claim: under the rule the reference's candidate j (main.cpp:413-429, 561-578) is rejected by both
-// rule sets whatever the running minima are: if dist_r <= r^2 at all, then RN(T_r - X_r) < eps and
-// RN(T_r + X_r) < eps strictly (SIMD accepts only it > eps, scalar only !(it < eps)).
-// With a = |C|, c* = a^2, T* = C.D exact, |D|^2 = 1 + k, |k| <= K = 2^-16, u = 2^-24:
-//  (1) the lane's values: cc within 3.01u c* of c*, T within 3.01u a|D| of T*.  The rule gives T < 0
-//      and |d| < 2.001 a eps, so |r^2 - c*| <= 2.01 a eps + 324u c*: with r in [16.1 eps, 16],
-//      14.9 eps <= a <= 16.01 (no product underflows, and 3.01u a <= 0.029 eps);
-//  (2) the reference: T_r = dot3 within 3.01u a of T*; its dist_r (exact ops on C) is within 8u c* of
-//      |C - D T_r|^2 >= c* - T*^2 / (1 + k) (q's two roundings 4.1u c*, the dot's three 3.1u c*:
-//      the 13.3u M term above with M = c*), so
-//        r^2 - dist_r <= r^2 - c* (1 - 8u - 1.03K) + T*^2;
-//      X_r = RN(sqrt(RN(r^2 - dist_r))) <= sqrt((r^2 - dist_r)(1 + 3.3u)), and by (1)
-//      3.3u (r^2 - dist_r) <= 3.4u c* + 6.7u a eps, so X_r^2 <= T*^2 + Delta,
-//        Delta = r^2 - c* (1 - 11.4u - 1.03K) + 6.7u a eps;
-//  (3) kappa: cc kappa <= c* (1 + 3.01u)(1 - 320u) <= c* (1 - 316u), and 1.03K + 11.4u = 275.1u, so
-//      rho - cc kappa >= Delta + 40u c*  (6.7u a eps <= 0.45u c* by a >= 14.9 eps);
-//  (4) Delta <= 0: X_r <= |T*|, T_r + X_r <= 3.01u a <= 0.029 eps.  Else sqrt(T*^2 + Delta) <=
-//      |T*| + Delta / (2|T*|) and the rule gives Delta + 40u c* <= d (1 + u) < |T| lambda (1 + 2.1u)
-//      <= (|T*| + 3.01u a) lambda (1 + 2.1u), where 3.01u a lambda (1 + 2.1u) <= 0.4u c* is inside the
-//      40u c*: Delta < |T*| lambda (1 + 2.1u), hence
-//        T_r + X_r <= 3.01u a + lambda (1 + 2.1u) / 2 <= 0.029 eps + 0.9501 eps < eps (1 - 2u),
-//      and RN of a sum below eps (1 - 2u) is below eps; T_r - X_r <= T_r + X_r.  dist_r == r^2 (the
-//      scalar rules' hit) has X_r = 0 and T_r <= 0.029 eps + T* < eps.
-// The square root is the reference's correctly rounded one; the kernel's own candidate code is not
-// involved -- a dropped lane runs no candidate for j unless another lane flags the pair, and then its
-// exact test reproduces this rejection.  tests/test_own_sphere_skip.py checks the claim on rays formed
-// as the reference forms them.
-//
-// Expanded (scene-wide tables; rtk_walk.h pair_prefilter_x, the walk-specialised kernels).  A second table
-// *xtab of the same entries, in front of it one row {c0, 0}: c0 = the midpoint of the bounding box of all
-// entry centres (cluster and member; f32).  Centres are S' = RN(S - c0), the kernel forms O' = RN(O - c0),
-//   T^ = fma(S'x, Dx, fma(S'y, Dy, fma(S'z, Dz, p))),          p = -RN-chain(O'.D)
-//   A^ = fma(S'x, -2O'x, fma(S'y, -2O'y, fma(S'z, -2O'z, oo))), oo = RN-chain(|O'|^2)
-//   e' = fma(-T^, T^, A^)
-// and skips on e' >= t' = RN+(t - |S'|^2 + G), t the entry's threshold above; behind on T^ < b' = b - H.
-// Mask rows, ranges, slots and rho are copied.  Bounds: a = max |S'| over the entries, b >= |O'| over every
-// origin (each lies on a scene sphere: sqrt(bound_m(c0)), the slack of M included), R = a + b, m = sqrt(M) of
-// the entry (M_j or M_c above: |C| <= m), C^ = S' - O' as a real vector.  Roundings (u each, |D| <= 1 + K/2):
-//  - S' and O': |C^ - (S - O)| <= u (|S'| + |O'|) <= u R, so |C^ - C_r| <= 1.01u (R + m) =: d for the
-//    reference's C_r = RN(S - O), and |C^| <= m (1 + 1e-3) inside M's own slack (R <= 10m where the table is used, below);
-//  - the chains: p and oo carry three roundings of partial sums <= |O'||D| and |O'|^2: 3.01u b|D|, 3.01u b^2;
-//    T^ adds three of partial sums <= (a + b)|D|:  |T^ - C^.D| <= 3.01u (a + 2b)|D| =: eT;
-//    A^ adds three of partial sums <= b^2 + 2ab:    |A^ - (|C^|^2 - |S'|^2)| <= u (6.02 b^2 + 6.02 ab);
-//  - the product T^2 is exact inside the last FMA, whose one rounding is of |A^ - T^2| <= max(a, m)^2 (1.01):
-//    u 1.01 max(a, m)^2;  and |T^2 - (C^.D)^2| <= eT (2|C^||D| + eT) <= 6.1u (a + 2b) m.
-//   Hence e' + |S'|^2 is within  u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m)  of f(C^) = |C^|^2 - (C^.D)^2.
-//  - f(C^) - l(O + C^) = (C^.D)^2 (1 - 1/|D|^2), at most K|C^|^2 <= K M (1 + 2.1e-3) in size;
-//  - member j: sqrt(l(O + C_r)) >= sqrt(l(O + C^)) - d, i.e. l(O + C_r) >= l(O + C^) - 2 d m - d^2, and the
-//    reference's dist_j >= l(O + C_r) - 13.3u M_j as above: the M-only terms (K (1 + 2.1e-3) + 13.3u + 2.02u) M_j
-//    (K + 15.9u) stay inside E_j = M_j (32u + 1.01K), which t already holds, and what is left is
-//      G >= u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m + 2.02 R m) + d^2;
-//  - cluster c: the proof above needs sqrt(l(q_c)) >= rho_c - u sqrt(M_c); now the point moves by u R 1.01, so
-//    it needs l(O + Q^) >= (rho_c + 1.01u R)^2, and rho_c <= 1.01 m: 2.05u R m more, M-only terms K M_c (1 + 2.1e-3).
-//  G = 1.25 u (6.02 b^2 + 6.02 ab + 1.01 max(a, m)^2 + 6.1 (a + 2b) m + 2.1 R m) per entry covers both (the head-room
-//  of 32u over the 23.5u derived above; d^2 <= 1.1 u^2 (R + m)^2 vanishes in it).  t' is rounded up after
-//  t - |S'|^2 + G is formed in f64 (|S'|^2 exact to 2^-52); t itself was rounded up.
-//  - behind: T^ is within eT + u R |D| <= u (4.02a + 7.03b)(1 + K) of (S - O).D where the proofs above allowed
-//    the prefilter's T 4u sqrt(M)|D|; H = u (4.5a + 7.5b) lowers every b by the whole new error (the old
-//    allowance is kept as slack), rounded down.
-// *x_ok (the launch fact "proven and useful", rt_kernel.h kPrefilterExpanded): every value of the table is
-// finite; G <= E/4 for every entry, E = M (32u + 1.01K) the slack already in t -- so the expanded form flags
-// at most what a threshold 1.25 E would, and R <= 10m as used above; and the scene lies near the origin of
-// its own coordinates.  The last is the premise's own margin: recentring makes G itself independent of where
-// the scene lies, but "every origin lies on a scene sphere" holds for an f32 origin only to its rounding,
-// (sqrt(3)/2) ulp(L) with L = max_i (|s_i|_inf + r_i), which M's slack (1e-3 + 1e-3 reach) was sized to absorb
-// for scenes near the origin and which the step |C^| <= m (1 + 1e-3) above draws on once more.  The expanded
-// table is used only where that rounding is below 1e-4, a tenth of the slack's absolute part (L < 1024);
-// a scene placed far from its own extent's scale keeps the plain table and the run-time kernel.
-// k_override / sub_override: rt_device_options ClusterCount / SubClusterSpheres (0: per scene, below).
-constexpr float kOwnR2Min = 2.6e-6f, kOwnR2Max = 256.0f;  // r in [16.1 eps, 16]
-static uint32_t cluster_table(const std::vector<float> &gv, uint32_t n_groups, std::vector<float> &tab,
-                              uint32_t *words, bool relative = false, uint32_t *levels = nullptr,
-                              uint32_t *sub_pairs = nullptr, uint32_t k_override = 0, uint32_t sub_override = 0,
-                              std::vector<float> *own_rho = nullptr, std::vector<float> *xtab = nullptr,
-                              bool *x_ok = nullptr) {
-    if (xtab) xtab->clear();
-    if (x_ok) *x_ok = false;
-    if (levels) *levels = 0;
-    if (sub_pairs) *sub_pairs = 0;
-    if (own_rho) own_rho->assign(4u * (size_t)n_groups, INFINITY);
-    tab.clear();
-    *words = n_groups <= 32u ? 1u : n_groups <= 64u ? 2u : 4u;
-    if (n_groups > kClMaxGroups) return 0;
-    struct Sph {
-        uint32_t s;
-        double x, y, z, r, m;
-    };
-    std::vector<Sph> sp;
-    for (uint32_t s = 0; s < 4u * n_groups; ++s) {
-        const uint32_t g = (s / 4u) * 4u * kGroupF4, l = s % 4u;
-        if (!std::isfinite(gv[g + 4u * kRowR2P + l])) continue;  // never flagged (-inf)
-        sp.push_back({s, gv[g + 4u * kRowX + l], gv[g + 4u * kRowY + l], gv[g + 4u * kRowZ + l],
-                      std::sqrt((double)std::max(gv[g + 4u * kRowR2 + l], 0.0f)), 0.0});
-    }
-    const uint32_t n = (uint32_t)sp.size();
-    if (n < 8u) return 0;
-    // reach of every origin (a point on some hittable sphere) from point p, with
-    // the same slack for origin rounding as prefilter_rows
-    auto bound_m = [&](double px, double py, double pz) {
-        double reach = 0.0;
-        for (const Sph &o : sp)
-            reach = std::max(reach, std::sqrt((o.x - px) * (o.x - px) + (o.y - py) * (o.y - py) + (o.z - pz) * (o.z - pz)) + o.r);
-        return (reach * 1.001 + 1e-3) * (reach * 1.001 + 1e-3);
-    };
-    const double u = 0x1p-24, K = 0x1p-16;
-    if (!relative)
-        for (Sph &o : sp) o.m = bound_m(o.x, o.y, o.z);
-    auto sigma = [&](const Sph &o) {
-        return relative ? o.r : std::sqrt(o.r * o.r + 13.3 * u * o.m) + u * std::sqrt(o.m);
-    };
-    const double s_rel = std::sqrt(13.3 * u) + 2.0 * u, a_rel = s_rel * (1.0 + u) + u;
-    // max(1.25 sqrt(n), n/8) clusters: measured on C2 (N = 64) K = 6/8/10/12/16 ->
-    // 112.4k/113.8k/114.6k/114.5k/111.4k Mrays/s; at 200 spheres K = 17/28 ->
-    // 45.0k/46.9k; at C5 (256) K = 20/26/32/40 -> 30.1k/31.3k/32.4k/32.4k
-    // per-lane tables carry the height-slab test, which culls most clusters of a
-    // ground-plane scene, so fewer (larger) clusters pay there: RTWeekend (482
-    // spheres) K = 32/40/60/90 -> 17.8k/18.5k/17.8k/16.7k Mrays/s, hence n/12
-    // Two-level tables (two or more mask words, below) take fewer, larger top
-    // clusters over sub-clusters of 3 (scene-wide) or 4 (per-lane) spheres:
-    // RTWeekend K/S = 40/4, 28/3, 28/4, 24/4 -> 21.1k/21.9k/21.9k/21.7k (one level
-    // at K 40: 19.6k); C5 at 512 spp K/S = 32/4, 24/3, 28/3, 24/2 -> 47.4k/48.2k/
-    // 48.3k/48.3k (one level: 46.3k).
-    // two levels for tables of two or more mask words only: the kernel walks
-    // one-word tables (at most 32 groups) as one level (rtk_walk.h clustered_groups)
-    const bool two_levels = *words >= 2u;
-    const uint32_t div = two_levels ? (relative ? 17u : 10u) : (relative ? 12u : 8u);
-    uint32_t k = std::max(2u, std::max((uint32_t)std::lround(1.25 * std::sqrt((double)n)), n / div));
-    if (k_override) k = std::min(n, std::max(2u, k_override));  // A/B (rt_device_options ClusterCount)
-    // k-means (f64, fixed LCG restarts) of the spheres idx into k clusters,
-    // minimising the sum of rho_c^2; returns each sphere's label
-    uint64_t lcg = 0x9E3779B97F4A7C15ull;
-    auto rnd = [&](uint32_t m) {
-        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-        return (uint32_t)((lcg >> 33) % m);
-    };
-    auto kmeans = [&](const std::vector<uint32_t> &idx, uint32_t k, int restarts) {
-        const uint32_t m = (uint32_t)idx.size();
-        std::vector<uint32_t> best_lab(m, 0u);
-        double best_cost = INFINITY;
-        std::vector<double> cx(k), cy(k), cz(k);
-        std::vector<uint32_t> lab(m);
-        for (int restart = 0; restart < restarts; ++restart) {
-            for (uint32_t c = 0; c < k; ++c) {  // k-means++ style seeding (farthest of a few random picks)
-                uint32_t pick = rnd(m);
-                double far = -1.0;
-                for (int t = 0; t < 4 && c > 0; ++t) {
-                    const uint32_t cand = rnd(m);
-                    const Sph &o = sp[idx[cand]];
-                    double dmin = INFINITY;
-                    for (uint32_t q = 0; q < c; ++q)
-                        dmin = std::min(dmin, (o.x - cx[q]) * (o.x - cx[q]) + (o.y - cy[q]) * (o.y - cy[q]) +
-                                                  (o.z - cz[q]) * (o.z - cz[q]));
-                    if (dmin > far) {
-                        far = dmin;
-                        pick = cand;
-                    }
-                }
-                const Sph &o = sp[idx[pick]];
-                cx[c] = o.x;
-                cy[c] = o.y;
-                cz[c] = o.z;
-            }
-            for (int it = 0; it < 40; ++it) {
-                for (uint32_t i = 0; i < m; ++i) {
-                    const Sph &o = sp[idx[i]];
-                    double dmin = INFINITY;
-                    for (uint32_t c = 0; c < k; ++c) {
-                        const double d2 = (o.x - cx[c]) * (o.x - cx[c]) + (o.y - cy[c]) * (o.y - cy[c]) +
-                                          (o.z - cz[c]) * (o.z - cz[c]);
-                        if (d2 < dmin) {
-                            dmin = d2;
-                            lab[i] = c;
-                        }
-                    }
-                }
-                std::vector<double> sx(k, 0.0), sy(k, 0.0), sz(k, 0.0), cnt(k, 0.0);
-                for (uint32_t i = 0; i < m; ++i) {
-                    sx[lab[i]] += sp[idx[i]].x;
-                    sy[lab[i]] += sp[idx[i]].y;
-                    sz[lab[i]] += sp[idx[i]].z;
-                    cnt[lab[i]] += 1.0;
-                }
-                for (uint32_t c = 0; c < k; ++c)
-                    if (cnt[c] > 0.0) {
-                        cx[c] = sx[c] / cnt[c];
-                        cy[c] = sy[c] / cnt[c];
-                        cz[c] = sz[c] / cnt[c];
-                    }
-            }
-            std::vector<double> rho(k, 0.0);
-            for (uint32_t i = 0; i < m; ++i) {
-                const Sph &o = sp[idx[i]];
-                const uint32_t c = lab[i];
-                const double d = std::sqrt((o.x - cx[c]) * (o.x - cx[c]) + (o.y - cy[c]) * (o.y - cy[c]) +
-                                           (o.z - cz[c]) * (o.z - cz[c]));
-                rho[c] = std::max(rho[c], d + sigma(o));
-            }
-            double cost = 0.0;
-            for (uint32_t c = 0; c < k; ++c) cost += rho[c] * rho[c];
-            if (cost < best_cost) {
-                best_cost = cost;
-                best_lab = lab;
-            }
-        }
-        return best_lab;
-    };
-    // final clusters: f32 centres (what the kernel subtracts), exact thresholds
-    struct Cl {
-        float qx, qy, qz, t;
-        float b;                    // behind threshold (below)
-        float srho = 0.0f, ymid = 0.0f, yhalf = INFINITY;  // height-slab bound (relative tables, below)
-        std::vector<uint32_t> mem;  // sphere slots, ascending
-    };
-    // Behind thresholds: a member j cannot be accepted by a ray whose computed
-    // T_j + X_j stays below eps (it = T - X or T + X < eps), and X_j <= r_j(1+2u).
-    // With T_j within 4.2u sqrt(M_j)|D| of (S_j - O).D (one rounding in C_j, three
-    // in the dot) and the prefilter's FMA T_c within 4u sqrt(M_c)|D| of (q_c - O).D,
-    // (S_j - O).D <= (q_c - O).D + |S_j - q_c||D| gives: T_c < -b_c with
-    //   b_c = max_j (|S_j - q_c| + r_j)(1 + 2^-15) + 4.3u (sqrt(M_c) + sqrt(M_j))
-    // proves every member is behind every origin-side candidate (|D| <= 1 + 2^-17
-    // under the |D|^2 bound).  Per sphere (q_c = S_j): b_j = r_j(1 + 2^-15) + 8.6u sqrt(M_j).
-    std::vector<float> beta_of_slot(4u * n_groups, 0.0f);
-    for (const Sph &o : sp)
-        beta_of_slot[o.s] = relative ? std::nextafter((float)(-(o.r * (1.0 + 0x1p-15) + 4.3 * u) * (1.0 + 1e-6)), -INFINITY)
-                                     : std::nextafter((float)-(o.r * (1.0 + 0x1p-15) + 8.6 * u * std::sqrt(o.m)), -INFINITY);
-    // The bound rows of a cluster over the spheres idx (any set: a top cluster's
-    // bound covers every sphere under it, as a sub-cluster's covers its members).
-    auto make_cl = [&](const std::vector<uint32_t> &idx) {
-        Cl C;
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        for (uint32_t i : idx) {
-            sx += sp[i].x;
-            sy += sp[i].y;
-            sz += sp[i].z;
-        }
-        C.qx = (float)(sx / idx.size());
-        C.qy = (float)(sy / idx.size());
-        C.qz = (float)(sz / idx.size());
-        const double qx = C.qx, qy = C.qy, qz = C.qz;
-        auto delta = [&](uint32_t i) {
-            return std::sqrt((sp[i].x - qx) * (sp[i].x - qx) + (sp[i].y - qy) * (sp[i].y - qy) +
-                             (sp[i].z - qz) * (sp[i].z - qz));
-        };
-        if (relative) {
-            double rho = 0.0, bmax = 0.0;
-            for (uint32_t i : idx) {
-                rho = std::max(rho, delta(i) * (1.0 + s_rel) + sp[i].r);
-                bmax = std::max(bmax, (delta(i) + sp[i].r) * (1.0 + 0x1p-15) + 4.3 * u * delta(i));
-            }
-            C.t = std::nextafter((float)(rho * rho * (1.0 + a_rel) * (1.0 + 1e-6)), INFINITY);
-            C.b = std::nextafter((float)(-(bmax + 4.3 * u) * (1.0 + 1e-6)), -INFINITY);
-            // Height slab.  A lane can accept member j only if its exact line passes
-            // within sigma_j = sqrt(r_j^2 + 13.3u |C_j|^2) <= r_j + k_s |C_j| of s_j
-            // (k_s = sqrt(13.3u) = 8.9e-4; the reference-rounded dist error, as above),
-            // so at some t with |O + tD - q_c| <= rho_s + k_s |C_j|, rho_s = max_j
-            // (delta_j + r_j), and height within [y_lo - k_s|C_j|, y_hi + k_s|C_j|]
-            // (y_lo/y_hi the members' extent).  Along the line the height O.y + t D.y
-            // over that t range lies within c +- |D.y| rho' (c = O.y + D.y T, T the
-            // projection of q_c): if |c - ymid| > yhalf + |D.y| rho' + E the line misses
-            // every member.  |C_j| <= |Q| + delta_j, |Q| <= (1 + cc)/2: the delta_j part
-            // is folded into srho / yhalf here, the |Q| part (twice, for height and t
-            // range) and the rounding of T, c, d and thr (< 2^-14 (1 + cc) + u |O.y|)
-            // into the kernel's per-lane E = cc kSlabRel + |O.y| 2^-21 + kSlabRel,
-            // kSlabRel = 2^-9 >= 2 (8.9e-4 (1.0001) / 2 + 2^-14).
-            double rs = 0.0, yhi = -INFINITY, ylo = INFINITY;
-            for (uint32_t i : idx) {
-                rs = std::max(rs, delta(i) + sp[i].r);
-                yhi = std::max(yhi, sp[i].y + sp[i].r);
-                ylo = std::min(ylo, sp[i].y - sp[i].r);
-            }
-            const double ks = 8.91e-4;
-            C.srho = std::nextafter((float)(rs * (1.0 + ks) * (1.0 + 0x1p-12)), INFINITY);
-            C.ymid = (float)((yhi + ylo) * 0.5);
-            const double half = std::max(yhi - (double)C.ymid, (double)C.ymid - ylo) + ks * rs;
-            C.yhalf = std::nextafter((float)(half * (1.0 + 0x1p-12)), INFINITY);
-        } else {
-            double rho = 0.0;
-            for (uint32_t i : idx) rho = std::max(rho, delta(i) + sigma(sp[i]));
-            const double mc = bound_m(qx, qy, qz);
-            rho = (rho + u * std::sqrt(mc)) * (1.0 + 1e-6);
-            C.t = std::nextafter((float)(rho * rho + mc * (32.0 * u + 1.01 * K)), INFINITY);
-            double bmax = 0.0;
-            for (uint32_t i : idx)
-                bmax = std::max(bmax, (delta(i) + sp[i].r) * (1.0 + 0x1p-15) + 4.3 * u * (std::sqrt(mc) + std::sqrt(sp[i].m)));
-            C.b = std::nextafter((float)-bmax, -INFINITY);
-        }
-        for (uint32_t i : idx) C.mem.push_back(sp[i].s);
-        return C;
-    };
-    const Cl pad_cl{0.0f, 0.0f, 0.0f, -INFINITY, 0.0f, 0.0f, 0.0f, INFINITY, {}};  // never entered
-    // top clusters
-    std::vector<uint32_t> all(n);
-    for (uint32_t i = 0; i < n; ++i) all[i] = i;
-    const std::vector<uint32_t> top_lab = kmeans(all, k, 16);
-    std::vector<std::vector<uint32_t>> tops;
-    for (uint32_t c = 0; c < k; ++c) {
-        std::vector<uint32_t> idx;
-        for (uint32_t i = 0; i < n; ++i)
-            if (top_lab[i] == c) idx.push_back(i);
-        if (!idx.empty()) tops.push_back(std::move(idx));
-    }
-    std::vector<Cl> cl;
-    for (const auto &idx : tops) cl.push_back(make_cl(idx));
-    if (cl.size() & 1u) cl.push_back(pad_cl);
-    // Second level (tables of two or more mask words): each top cluster's spheres
-    // in sub-clusters of about kSubSpheres (k-means inside the top cluster), their
-    // pair entries contiguous per top cluster, padded to whole pairs.
-    const bool two = two_levels;
-    uint32_t sub_spheres = relative ? 4u : 3u;
-    if (sub_override) sub_spheres = sub_override;  // A/B (rt_device_options SubClusterSpheres)
-    std::vector<std::vector<Cl>> sub(cl.size());
-    if (two)
-        for (size_t c = 0; c < tops.size(); ++c) {
-            const std::vector<uint32_t> &idx = tops[c];
-            const uint32_t k2 = std::min((uint32_t)idx.size(), ((uint32_t)idx.size() + sub_spheres - 1u) / sub_spheres);
-            if (k2 <= 1u) {
-                sub[c].push_back(make_cl(idx));
-            } else {
-                const std::vector<uint32_t> lab = kmeans(idx, k2, 8);
-                for (uint32_t q = 0; q < k2; ++q) {
-                    std::vector<uint32_t> part;
-                    for (size_t i = 0; i < idx.size(); ++i)
-                        if (lab[i] == q) part.push_back(idx[i]);
-                    if (!part.empty()) sub[c].push_back(make_cl(part));
-                }
-            }
-            if (sub[c].size() & 1u) sub[c].push_back(pad_cl);
-        }
-    for (Cl &C : cl) std::sort(C.mem.begin(), C.mem.end());
-    for (auto &v : sub)
-        for (Cl &C : v) std::sort(C.mem.begin(), C.mem.end());
-    const uint32_t n_cp = (uint32_t)cl.size() / 2u;
-    uint32_t n_sp = 0, n_mp = 0;
-    for (size_t c = 0; c < cl.size(); ++c) {
-        if (two) {
-            n_sp += (uint32_t)sub[c].size() / 2u;
-            for (const Cl &S : sub[c]) n_mp += ((uint32_t)S.mem.size() + 1u) / 2u;
-        } else {
-            n_mp += ((uint32_t)cl[c].mem.size() + 1u) / 2u;
-        }
-    }
-    const uint32_t ef = cl_entry_f4(*words, relative) * 4u;  // floats per entry
-    tab.assign((size_t)(n_cp + n_sp + n_mp) * ef, 0.0f);
-    auto put_u = [&](size_t at, uint32_t v) { memcpy(&tab[at], &v, 4); };
-    auto sphere_xyz = [&](uint32_t s, int axis) {
-        const uint32_t g = (s / 4u) * 4u * kGroupF4, l = s % 4u;
-        return gv[g + 4u * (uint32_t)axis + l];
-    };
-    // member threshold: the scene-wide r2p, or r^2 for the per-lane rule
-    auto sphere_r2p = [&](uint32_t s) {
-        return gv[(s / 4u) * 4u * kGroupF4 + 4u * (relative ? kRowR2 : kRowR2P) + s % 4u];
-    };
-    // the bound rows of a cluster pair entry (both levels)
-    auto put_pair = [&](uint32_t p, const Cl &A, const Cl &B) {
-        float *e = &tab[(size_t)p * ef];
-        e[0] = A.qx, e[1] = B.qx, e[2] = A.qy, e[3] = B.qy, e[4] = A.qz, e[5] = B.qz, e[6] = A.t, e[7] = B.t;
-        e[12] = A.b, e[13] = B.b;
-        if (relative) {  // the height-slab bound (rt_kernel.h: row 3 zw, row 4)
-            e[14] = A.srho, e[15] = B.srho;
-            e[16] = A.ymid, e[17] = B.ymid, e[18] = A.yhalf, e[19] = B.yhalf;
-        }
-    };
-    uint32_t next_sub = n_cp, next = n_cp + n_sp;
-    // the member pair entries of cluster C from entry `next` on; returns their count
-    auto put_members = [&](const Cl &C) {
-        const uint32_t cnt = ((uint32_t)C.mem.size() + 1u) / 2u;
-        for (uint32_t q = 0; q < cnt; ++q, ++next) {
-            float *m = &tab[(size_t)next * ef];
-            const size_t mb = (size_t)next * ef;
-            for (int w = 0; w < 2; ++w) {
-                const uint32_t idx = 2u * q + (uint32_t)w;
-                if (idx < C.mem.size()) {
-                    const uint32_t s = C.mem[idx];
-                    m[0 + w] = sphere_xyz(s, kRowX);
-                    m[2 + w] = sphere_xyz(s, kRowY);
-                    m[4 + w] = sphere_xyz(s, kRowZ);
-                    m[6 + w] = sphere_r2p(s);
-                    m[12 + w] = beta_of_slot[s];
-                    if (!relative) put_u(mb + 14u + (uint32_t)w, s);  // its slot (the own-sphere rule)
-                    // the u64 bit of pair q = s >> 1 in the row of word q >> 6 (row 2
-                    // for word 0, row 3 + w for word w >= 1; the other words' rows stay 0)
-                    const uint64_t bit = 1ull << ((s >> 1) & 63u);
-                    const uint32_t word = (s >> 1) >> 6;
-                    const size_t row = word == 0u ? 8u : 4u * (3u + word);
-                    put_u(mb + row + 2u * w, (uint32_t)bit);
-                    put_u(mb + row + 1u + 2u * w, (uint32_t)(bit >> 32));
-                } else {
-                    m[6 + w] = -INFINITY;  // padding member: never flagged, no bit
-                }
-            }
-        }
-        return cnt;
-    };
-    for (uint32_t p = 0; p < n_cp; ++p) {
-        put_pair(p, cl[2u * p], cl[2u * p + 1u]);
-        for (int h = 0; h < 2; ++h) {
-            const size_t c = 2u * p + (uint32_t)h;
-            if (!two) {
-                put_u((size_t)p * ef + 8u + 2u * h, next);
-                put_u((size_t)p * ef + 9u + 2u * h, put_members(cl[c]));
-                continue;
-            }
-            // a top cluster: its sub-cluster pair entries, then their members
-            const uint32_t first = next_sub, cnt = (uint32_t)sub[c].size() / 2u;
-            put_u((size_t)p * ef + 8u + 2u * h, first);
-            put_u((size_t)p * ef + 9u + 2u * h, cnt);
-            next_sub += cnt;
-            for (uint32_t q = 0; q < cnt; ++q) {
-                const uint32_t e = first + q;
-                put_pair(e, sub[c][2u * q], sub[c][2u * q + 1u]);
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    put_u((size_t)e * ef + 8u + 2u * h2, next);
-                    put_u((size_t)e * ef + 9u + 2u * h2, put_members(sub[c][2u * q + (uint32_t)h2]));
-                }
-            }
-        }
-    }
-    // the own-sphere rule's rho_j (above): r_j^2 for the members inside the proven radius range
-    if (own_rho && !relative)
-        for (const Sph &o : sp) {
-            const float r2 = gv[(o.s / 4u) * 4u * kGroupF4 + 4u * kRowR2 + o.s % 4u];
-            if (r2 >= kOwnR2Min && r2 <= kOwnR2Max) (*own_rho)[o.s] = r2;
-        }
-    // the expanded table (proof above, "Expanded"): every entry half with a finite threshold is a real
-    // cluster or member; padding halves keep centre 0 and -inf (never entered, never flagged)
-    if (xtab && x_ok && !relative) {
-        const uint32_t n_ent = n_cp + n_sp + n_mp;
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t e = 0; e < n_ent; ++e)
-            for (uint32_t w = 0; w < 2u; ++w) {
-                const float *en = &tab[(size_t)e * ef];
-                if (!std::isfinite(en[6 + w])) continue;
-                for (uint32_t ax = 0; ax < 3u; ++ax) {
-                    lo[ax] = std::min(lo[ax], (double)en[2u * ax + w]);
-                    hi[ax] = std::max(hi[ax], (double)en[2u * ax + w]);
-                }
-            }
-        const float c0[3] = {(float)(0.5 * (lo[0] + hi[0])), (float)(0.5 * (lo[1] + hi[1])), (float)(0.5 * (lo[2] + hi[2]))};
-        xtab->assign(4u + tab.size(), 0.0f);
-        float *xt = xtab->data() + 4u;
-        memcpy(xt, tab.data(), tab.size() * sizeof(float));
-        for (int ax = 0; ax < 3; ++ax) (*xtab)[(size_t)ax] = c0[ax];
-        double ra = 0.0;  // a = max |S'|
-        for (uint32_t e = 0; e < n_ent; ++e)
-            for (uint32_t w = 0; w < 2u; ++w) {
-                float *en = xt + (size_t)e * ef;
-                if (!std::isfinite(en[6 + w])) continue;
-                double ss = 0.0;
-                for (uint32_t ax = 0; ax < 3u; ++ax) {
-                    en[2u * ax + w] = (float)((double)en[2u * ax + w] - (double)c0[ax]);  // S' = RN(S - c0)
-                    ss += (double)en[2u * ax + w] * en[2u * ax + w];
-                }
-                ra = std::max(ra, std::sqrt(ss));
-            }
-        const double rb = std::sqrt(bound_m(c0[0], c0[1], c0[2])) * (1.0 + 1e-6);  // b >= |O'|
-        double place = 0.0;  // L = the largest coordinate an origin can have
-        for (const Sph &o : sp) place = std::max(place, std::max(std::fabs(o.x), std::max(std::fabs(o.y), std::fabs(o.z))) + o.r);
-        const float place_f = (float)place;
-        const double origin_rounding = 0.8661 * ((double)std::nextafter(place_f, INFINITY) - (double)place_f);
-        bool ok = std::isfinite(ra) && std::isfinite(rb) && origin_rounding <= 1e-4;
-        for (uint32_t e = 0; e < n_ent; ++e)
-            for (uint32_t w = 0; w < 2u; ++w) {
-                const float *src = &tab[(size_t)e * ef];
-                float *en = xt + (size_t)e * ef;
-                if (!std::isfinite(src[6 + w])) continue;
-                const double mm = bound_m(src[0 + w], src[2 + w], src[4 + w]), m = std::sqrt(mm);
-                const double am = std::max(ra, m);
-                const double g = 1.25 * u * (6.02 * rb * rb + 6.02 * ra * rb + 1.01 * am * am + 6.1 * (ra + 2.0 * rb) * m +
-                                             2.1 * (ra + rb) * m);
-                const double ss = (double)en[0 + w] * en[0 + w] + (double)en[2 + w] * en[2 + w] + (double)en[4 + w] * en[4 + w];
-                en[6 + w] = std::nextafter((float)((double)src[6 + w] - ss + g), INFINITY);
-                en[12 + w] = std::nextafter((float)((double)src[12 + w] - u * (4.5 * ra + 7.5 * rb)), -INFINITY);
-                ok = ok && g <= 0.25 * mm * (32.0 * u + 1.01 * K) && std::isfinite(en[0 + w]) && std::isfinite(en[2 + w]) &&
-                     std::isfinite(en[4 + w]) && std::isfinite(en[6 + w]) && std::isfinite(en[12 + w]);
-            }
-        *x_ok = ok && std::isfinite(c0[0]) && std::isfinite(c0[1]) && std::isfinite(c0[2]);
-    }
-    if (levels) *levels = two ? 2u : 1u;
-    if (sub_pairs) *sub_pairs = n_sp;
-    return n_cp;
-}
-
-// Whether every r^2 the exact test can accept is 0 or in [2^-36, 2^60]: then
-// a passing candidate's r^2 - dist is 0 or >= 2^-60 (it is >= ulp(r^2)/2 when
-// positive), the range where the kernel's short sqrt is verified exact.
-static uint32_t sqrt_range_ok(const std::vector<float> &gv, uint32_t n_groups, bool simd) {
-    for (uint32_t s = 0; s < 4u * n_groups; ++s) {
-        const float r2 = gv[(s / 4u) * 4u * kGroupF4 + 4u * kRowR2 + s % 4u];
-        if (!(simd ? r2 > 0.0f : r2 >= 0.0f)) continue;  // never accepted (padding)
-        if (r2 != 0.0f && !(r2 >= 0x1p-36f && r2 <= 0x1p60f)) return 0u;
-    }
-    return 1u;
-}
-
-// One rule set of a scene in the kernel's layout (see rt_kernel.h): rs 0 =
-// SIMD rules from SIMDSpheres (main.cpp:399-400) + Materials[4g+l]
-// (main.cpp:443-444); rs 1 = scalar rules from ScalarSpheres[s].Position/
-// Radius/Material (main.cpp:547-590), padding lanes r^2 = -inf (the kernel
-// also skips them by its s < n_spheres test: the scalar loop runs to Count).
-struct PackedSet {
-    std::vector<float> groups, mats;
-    uint32_t n_groups = 0;
-    bool prefilter_pays = false;
-    bool relative = false;  // the threshold row (kRowR2P) rewritten to r^2 / -inf for the per-lane threshold
-    uint32_t fast_sqrt = 0;
-    std::vector<float> clusters;  // cluster_table
-    uint32_t n_cpairs = 0, cl_words = 0;
-    uint32_t cl_levels = 0, cl_sub_pairs = 0;  // two-level tables (cl_words >= 2)
-    std::vector<float> own_rho;  // per slot: word 3 of the sphere record's centre row (cluster_table, "own sphere")
-    // the expanded table of a scene-wide table (cluster_table, "expanded"): the row {c0, 0}, then the entries;
-    // empty without one.  clusters_x_ok: proven and useful (the launch fact kPrefilterExpanded)
-    std::vector<float> clusters_x;
-    bool clusters_x_ok = false;
-};
-
-static int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env = -1, uint32_t cluster_k = 0,
-                    uint32_t sub_spheres = 0) {
-    const uint32_t ng = scene->SIMDSpheres.Count;
-    const uint32_t ns = scene->ScalarSpheres.Count;
-    if (ng == 0 || !scene->SIMDSpheres.Data || !scene->Materials.Data || ns == 0 || !scene->ScalarSpheres.Data)
-        return fail(RT_EINVAL, "scene: empty scene");
-    const uint32_t ngs = (ns + 3u) / 4u;
-    if (ng > kMaxGroups || ngs > kMaxGroups)
-        return fail(RT_EINVAL, "scene: %u spheres exceed the limit of %u", ns, 4u * kMaxGroups);
-    const uint32_t n = rs == 0 ? ng : ngs;
-    p.n_groups = n;
-    p.groups.assign((size_t)n * 4 * kGroupF4, 0.0f);
-    p.mats.assign((size_t)n * 16u * kSphereF4, 0.0f);  // sphere records (rt_kernel.h kSphereF4)
-    std::vector<float> &gv = p.groups;
-    if (rs == 0) {
-        const rt_sphere_group *g = (const rt_sphere_group *)scene->SIMDSpheres.Data;
-        const rt_material *m = (const rt_material *)scene->Materials.Data;
-        for (uint32_t i = 0; i < ng; ++i) {
-            for (int l = 0; l < 4; ++l) {
-                gv[i * 4 * kGroupF4 + 4 * kRowX + l] = g[i].X[l];
-                gv[i * 4 * kGroupF4 + 4 * kRowY + l] = g[i].Y[l];
-                gv[i * 4 * kGroupF4 + 4 * kRowZ + l] = g[i].Z[l];
-                gv[i * 4 * kGroupF4 + 4 * kRowR2 + l] = g[i].Radii[l] * g[i].Radii[l];
-                const uint32_t s = 4u * i + (uint32_t)l;
-                float *rec = &p.mats[(size_t)s * 4u * kSphereF4];
-                rec[0] = g[i].X[l];
-                rec[1] = g[i].Y[l];
-                rec[2] = g[i].Z[l];
-                if (s < scene->Materials.Count) put_material(rec + 4, m[s]);
-            }
-        }
-    } else {
-        const rt_scalar_sphere *s = (const rt_scalar_sphere *)scene->ScalarSpheres.Data;
-        for (uint32_t i = 0; i < ns; ++i) {
-            const uint32_t gi = i / 4u, l = i % 4u;
-            gv[gi * 4 * kGroupF4 + 4 * kRowX + l] = s[i].Position.x;
-            gv[gi * 4 * kGroupF4 + 4 * kRowY + l] = s[i].Position.y;
-            gv[gi * 4 * kGroupF4 + 4 * kRowZ + l] = s[i].Position.z;
-            gv[gi * 4 * kGroupF4 + 4 * kRowR2 + l] = s[i].Radius * s[i].Radius;
-            float *rec = &p.mats[(size_t)i * 4u * kSphereF4];
-            rec[0] = s[i].Position.x;
-            rec[1] = s[i].Position.y;
-            rec[2] = s[i].Position.z;
-            put_material(rec + 4, s[i].Material);
-        }
-        for (uint32_t i = ns; i < ngs * 4u; ++i) gv[(i / 4u) * 4 * kGroupF4 + 4 * kRowR2 + (i % 4u)] = -__builtin_inff();
-    }
-    p.prefilter_pays = prefilter_rows(gv, n, rs == 0);
-    p.fast_sqrt = sqrt_range_ok(gv, n, rs == 0);
-    // Where the scene-wide bound M_j makes r2p useless (a huge sphere: RTWeekend's
-    // ground), the thresholds are formed per lane from the lane's own |C|^2 instead
-    // (rtk_walk.h kPfRel, kClRel): the cluster table is built for that rule, and
-    // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
-    p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
-    p.n_cpairs = cluster_table(gv, n, p.clusters, &p.cl_words, p.relative, &p.cl_levels, &p.cl_sub_pairs, cluster_k,
-                               sub_spheres, &p.own_rho, &p.clusters_x, &p.clusters_x_ok);
-    if (!p.n_cpairs) {
-        p.clusters_x.clear();
-        p.clusters_x_ok = false;
-    }
-    // (a record per real sphere of the scalar set, per slot of the SIMD set; without a table every rho is +inf)
-    for (uint32_t sl = 0; sl < (rs == 0 ? 4u * n : ns); ++sl) p.mats[(size_t)sl * 4u * kSphereF4 + 3u] = p.own_rho[sl];
-    if (p.relative)
-        for (uint32_t sl = 0; sl < 4u * n; ++sl) {
-            const size_t base = (size_t)(sl / 4u) * 4u * kGroupF4 + sl % 4u;
-            gv[base + 4u * kRowR2P] = std::isfinite(gv[base + 4u * kRowR2P]) ? gv[base + 4u * kRowR2] : -INFINITY;
-        }
+    if (nf4) HIP_OK(hipMemcpyAsync(buf, tab.data(), nf4 * 16u, hipMemcpyHostToDevice, d->stream));
     return RT_OK;
 }
 
@@ -1155,39 +469,16 @@ extern "C" int rt_scene_upload(rt_device *d, const rt_scene *scene) {
         d->fast_sqrt[rs] = ps[rs].fast_sqrt;
         const int rc = upload_set(d, rs, ps[rs].groups, ps[rs].mats, ps[rs].n_groups);
         if (rc) return rc;
-        const size_t nf4 = ps[rs].clusters.size() / 4u;
+        const ClusterTable &cl = ps[rs].cl;  // (without a table, tab and xtab are empty: rt_pack.h)
         d->n_cpairs[rs] = 0;
-        if (nf4 > d->cap_clusters[rs]) {
-            HIP_OK(hipStreamSynchronize(d->stream));
-            (void)hipFree(d->d_clusters[rs]);
-            d->d_clusters[rs] = nullptr;
-            d->cap_clusters[rs] = 0;
-            if (hipMalloc(&d->d_clusters[rs], nf4 * 16u) != hipSuccess)
-                return fail(RT_ENOMEM, "rt_scene_upload: device allocation failed");
-            d->cap_clusters[rs] = nf4;
+        if (const int rc2 = upload_table(d, d->d_clusters[rs], d->cap_clusters[rs], cl.tab)) return rc2;
+        if (!cl.tab.empty()) {
+            d->n_cpairs[rs] = cl.n_cpairs;
+            d->cl_words[rs] = cl.words;
         }
-        if (nf4) {
-            HIP_OK(hipMemcpyAsync(d->d_clusters[rs], ps[rs].clusters.data(), nf4 * 16u, hipMemcpyHostToDevice,
-                                  d->stream));
-            d->n_cpairs[rs] = ps[rs].n_cpairs;
-            d->cl_words[rs] = ps[rs].cl_words;
-        }
-        const size_t xf4 = ps[rs].clusters_x.size() / 4u;
         d->clusters_x_ok[rs] = false;
-        if (xf4 > d->cap_clusters_x[rs]) {
-            HIP_OK(hipStreamSynchronize(d->stream));
-            (void)hipFree(d->d_clusters_x[rs]);
-            d->d_clusters_x[rs] = nullptr;
-            d->cap_clusters_x[rs] = 0;
-            if (hipMalloc(&d->d_clusters_x[rs], xf4 * 16u) != hipSuccess)
-                return fail(RT_ENOMEM, "rt_scene_upload: device allocation failed");
-            d->cap_clusters_x[rs] = xf4;
-        }
-        if (xf4 && nf4) {
-            HIP_OK(hipMemcpyAsync(d->d_clusters_x[rs], ps[rs].clusters_x.data(), xf4 * 16u, hipMemcpyHostToDevice,
-                                  d->stream));
-            d->clusters_x_ok[rs] = ps[rs].clusters_x_ok;
-        }
+        if (const int rc2 = upload_table(d, d->d_clusters_x[rs], d->cap_clusters_x[rs], cl.xtab)) return rc2;
+        d->clusters_x_ok[rs] = !cl.xtab.empty() && cl.x_ok;
     }
     HIP_OK(hipStreamSynchronize(d->stream));
     d->n_spheres = scene->ScalarSpheres.Count;
@@ -1203,100 +494,6 @@ extern "C" int rt_scene_upload(rt_device *d, const rt_scene *scene) {
         d->reserve_tiles = 0;
         d->reserve_pixels = 0;
     }
-    return RT_OK;
-}
-
-extern "C" int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, float *out_r2, float *out_r2p,
-                                  uint32_t capacity, uint32_t *out_count, uint32_t *out_flags) {
-    if (!scene || !out_count) return fail(RT_EINVAL, "rt_scene_prefilter: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    const uint32_t n = 4u * p.n_groups;
-    *out_count = n;
-    if (out_flags) *out_flags = (p.prefilter_pays ? 1u : 0u) | (p.fast_sqrt ? 2u : 0u) | (p.relative ? 4u : 0u);
-    if ((out_r2 || out_r2p) && capacity < n) return fail(RT_EINVAL, "rt_scene_prefilter: capacity %u < %u", capacity, n);
-    for (uint32_t s = 0; s < n; ++s) {
-        const size_t base = (size_t)(s / 4u) * 4u * kGroupF4 + s % 4u;
-        if (out_r2) out_r2[s] = p.groups[base + 4u * kRowR2];
-        if (out_r2p) out_r2p[s] = p.groups[base + 4u * kRowR2P];
-    }
-    return RT_OK;
-}
-
-extern "C" int rt_scene_own_sphere(const rt_scene *scene, uint32_t enable_simd, float *out_rho, uint32_t capacity,
-                                   uint32_t *out_count) {
-    if (!scene || !out_count) return fail(RT_EINVAL, "rt_scene_own_sphere: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    const uint32_t n = 4u * p.n_groups;
-    *out_count = n;
-    if (out_rho && capacity < n) return fail(RT_EINVAL, "rt_scene_own_sphere: capacity %u < %u", capacity, n);
-    for (uint32_t s = 0; out_rho && s < n; ++s) out_rho[s] = p.own_rho[s];
-    return RT_OK;
-}
-
-extern "C" int rt_scene_groups(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
-                               uint32_t *out_f4, uint32_t *out_rows) {
-    if (!scene || !out_f4) return fail(RT_EINVAL, "rt_scene_groups: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    const uint32_t nf4 = p.n_groups * kGroupF4;
-    *out_f4 = nf4;
-    if (out_rows) {
-        const uint32_t rows[6] = {kGroupF4, kRowX, kRowY, kRowZ, kRowR2, kRowR2P};
-        memcpy(out_rows, rows, sizeof rows);
-    }
-    if (out) {
-        if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_groups: capacity %u < %u", capacity_f4, nf4);
-        memcpy(out, p.groups.data(), (size_t)nf4 * 16u);
-    }
-    return RT_OK;
-}
-
-extern "C" int rt_scene_clusters(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
-                                 uint32_t *out_f4, uint32_t *out_cpairs) {
-    if (!scene || !out_f4 || !out_cpairs) return fail(RT_EINVAL, "rt_scene_clusters: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    const uint32_t nf4 = (uint32_t)(p.clusters.size() / 4u);
-    *out_f4 = nf4;
-    *out_cpairs = p.n_cpairs;
-    if (out) {
-        if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_clusters: capacity %u < %u", capacity_f4, nf4);
-        memcpy(out, p.clusters.data(), (size_t)nf4 * 16u);
-    }
-    return RT_OK;
-}
-
-extern "C" int rt_scene_clusters_expanded(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
-                                          uint32_t *out_f4, float *out_c0, uint32_t *out_in_use) {
-    if (!scene || !out_f4 || !out_c0 || !out_in_use) return fail(RT_EINVAL, "rt_scene_clusters_expanded: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    const uint32_t nf4 = p.clusters_x.empty() ? 0u : (uint32_t)(p.clusters_x.size() / 4u) - 1u;
-    *out_f4 = nf4;
-    *out_in_use = p.clusters_x_ok ? 1u : 0u;
-    for (int ax = 0; ax < 3; ++ax) out_c0[ax] = nf4 ? p.clusters_x[(size_t)ax] : 0.0f;
-    if (out) {
-        if (capacity_f4 < nf4) return fail(RT_EINVAL, "rt_scene_clusters_expanded: capacity %u < %u", capacity_f4, nf4);
-        if (nf4) memcpy(out, p.clusters_x.data() + 4u, (size_t)nf4 * 16u);
-    }
-    return RT_OK;
-}
-
-extern "C" int rt_scene_cluster_layout(const rt_scene *scene, uint32_t enable_simd, uint32_t *out_levels,
-                                       uint32_t *out_sub_pairs) {
-    if (!scene || !out_levels || !out_sub_pairs) return fail(RT_EINVAL, "rt_scene_cluster_layout: NULL argument");
-    PackedSet p;
-    const int rc = pack_set(scene, enable_simd ? 0 : 1, p);
-    if (rc) return rc;
-    *out_levels = p.n_cpairs ? p.cl_levels : 0u;
-    *out_sub_pairs = p.cl_sub_pairs;
     return RT_OK;
 }
 

@@ -5,55 +5,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
-enum { kSrcSmem = 0, kSrcLds = 1 };  // where the sphere loop reads its groups
-constexpr uint32_t kGroupF4 = 5;      // float4 rows per sphere group:
-constexpr uint32_t kRowX = 0, kRowY = 1, kRowZ = 2;  //   centres
-constexpr uint32_t kRowR2 = 3;        //   r*r (rows 0-3 = one s_load_dwordx16: all the exact test reads)
-constexpr uint32_t kRowR2P = 4;       //   prefilter thresholds (the per-group prefilter loop only)
-constexpr uint32_t kSphereF4 = 4;     // float4 rows per sphere record (TraceArgs.materials)
-enum { kFlagAccumZero = 1, kFlagSrgbPow = 2 };
-// Clustered secondary-ray prefilter (rt_host.cpp cluster_table): entries of
-// cl_entry_f4(W) float4 rows, read through the scalar cache --
-//   cluster pair c : {qx0 qx1 qy0 qy1} {qz0 qz1 rc2p0 rc2p1} {first0 count0 first1 count1} {b0 b1 0 0} [padding]
-//   member pair m  : {x0 x1 y0 y1}     {z0 z1 r2p0 r2p1}     {word-0 bits of member 0 (lo, hi), of member 1}
-//                    {b0 b1 slot0 slot1}  then one row per further word w = 1 .. W-1: {word-w bits of member 0, of member 1}
-// (slot = the member's sphere slot 4*group + lane as a u32, scene-wide tables only (else 0): a lane that has
-// proven it cannot accept the sphere its ray leaves drops that slot from its own flags -- rtk_walk.h own_sphere)
-// (b = behind threshold: a lane whose prefilter T = (centre - O).D is below
-// it cannot accept any member -- rt_host.cpp cluster_table)
-// (first/count index member-pair entries; a member's pair q = sphere slot >> 1
-// is its sphere pair in group order, the bit it sets in the wave's pair mask).
-// The wave mask is kept in SGPRs, W = cl_words u64 words of it (1: n_groups <= 32,
-// 2: <= 64, 4: <= 128): member k's pair q sets bit q & 63 of word q >> 6, and its
-// entry holds that bit in the row of word q >> 6 and 0 in the others, so the kernel
-// merges a flagged member into every word with one select and one OR each.
-// With pf_relative the thresholds are per lane: rc2p / r2p hold R_c / r^2 and
-// b the M-free behind bases (rt_host.cpp cluster_table, "relative"), and a
-// cluster pair also carries its height-slab bound (rtk_walk.h cluster_slab):
-//   row 3 = {b0 b1 srho0 srho1}, row 4 = {ymid0 ymid1 yhalf0 yhalf1}
-// (entries then have at least 5 rows; member entries leave row 4 to the bits).
-// padding members: threshold -inf, bits 0.
-constexpr uint32_t cl_entry_f4(uint32_t words, bool relative = false) {
-    return words == 1u ? (relative ? 5u : 4u) : 3u + words;
-}
-constexpr float kSlabRel = 0x1p-9f;  // the slab test's per-lane margin per unit of cc (rt_host.cpp cluster_table)
-constexpr uint32_t kClMaxGroups = 128;   // table built up to this many groups
-constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_host.cpp clusters_env; RTWeekend's
-                                         // 121 groups: 11.3k Mrays/s clustered against 9.4k per group)
+#include "rt_layout.h"
 
-// HBM layout of an uploaded scene (per rule set):
-//   groups    : n_groups x 5 float4 = {x[4]}, {y[4]}, {z[4]}, {r*r[4]}, {r2p[4]}  (80 B/group)
-//               rows 0-3 are what an exact test reads (the cluster walk's recheck: one scalar load);
-//               r2p = prefilter threshold of the secondary-ray sphere loop (rt_host.cpp);
-//               with pf_relative, r*r again (-inf: never hit) and the threshold is formed per lane
-//   spheres   : 4*n_groups records of kSphereF4 float4 = {centre.xyz, rho}, {Color.xyz, Specular},
-//               {Emissive.xyz, IOR}, {1/IOR, r0 outside, r0 inside, 0} (dielectrics; else 0)
-//               rho = r*r where the own-sphere rule applies to the sphere, +inf where it is off
-//               (rt_host.cpp cluster_table, "own sphere"; rt_scene_own_sphere reports it)
-//               (64 B/sphere: what shading gathers for the winning sphere,
-//               addressed by one shift of its index; TraceArgs.materials)
-// r*r is precomputed on the host with the same f32 multiply the reference
-// repeats per test (main.cpp:406), so it is bit-identical.
+enum { kSrcSmem = 0, kSrcLds = 1 };  // where the sphere loop reads its groups
+enum { kFlagAccumZero = 1, kFlagSrgbPow = 2 };
+// (the scene and table layouts the host packs: rt_layout.h)
 struct TraceArgs {
     const float4 *groups;
     const float4 *materials;
@@ -169,7 +125,7 @@ constexpr uint32_t kCullTotals = 128;
 constexpr uint32_t kCullFolded = 130;  // a per-tile launch's folded segments (rtk_launch_empty_counts), per launch
 // TraceArgs.prefilter: off, on, or on with `clusters` naming the expanded table -- the scene-wide
 // table recentred on c0, `clusters` naming the float4 row {c0, 0} and entry 0 the row behind it, its thresholds those of the
-// 7-op estimate (rtk_walk.h pair_prefilter_x; rt_host.cpp cluster_table, "expanded").  The host sets
+// 7-op estimate (rtk_walk.h pair_prefilter_x; rt_pack.cpp expand_table).  The host sets
 // the last only where that table exists and is proven and useful for the scene, and only for a
 // launch of a kernel that reads it (below); every other kernel tests the field as a boolean.
 enum { kPrefilterOff = 0, kPrefilterOn = 1, kPrefilterExpanded = 2 };
@@ -203,7 +159,7 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 //   expanded table  the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4) hold the expanded prefilter alone:
 //                   they run only where `clusters` is the expanded table (prefilter == kPrefilterExpanded:
 //                   it exists, every value of it is finite, and its extra slack G stays within a quarter
-//                   of each entry's own E -- rt_host.cpp cluster_table).  A scene-wide table without that
+//                   of each entry's own E -- rt_pack.cpp expand_table).  A scene-wide table without that
 //                   (a scene placed far from its own extent's scale) is walked by the run-time kernel
 //                   on the table as it always was.
 // and the kernels exist only for the culled production shapes (rtk_walk_shape).  Every other launch
@@ -272,10 +228,8 @@ static inline size_t rtk_lds_bytes(const TraceArgs *a) {
 // The largest scene the LDS image holds (64 KB of dynamic LDS per block with
 // the two tables): 265 groups = 1,060 spheres.  Larger scenes stay in HBM
 // (scene_in_lds = 0): the sphere loop reads groups through the scalar cache as
-// always, and the per-lane gathers go through L1/L2.  Up to kMaxGroups groups
-// (the primary cull masks are rtk_mask_words(kMaxGroups) = 128 words per wave tile).
+// always, and the per-lane gathers go through L1/L2.  Up to kMaxGroups groups (rt_layout.h).
 static const uint32_t kMaxLdsGroups = (65536u - 8192u - 2048u) / (16u * kGroupF4 + 64u * kSphereF4);  // 164 groups
-static const uint32_t kMaxGroups = 4096u;                                                    // 16,384 spheres
 
 extern "C" int rtk_launch_trace(const TraceArgs *a, int simd, int src, int cull, int lanes_per_pixel,
                                 hipStream_t stream);
@@ -354,8 +308,6 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
-// sets rt_last_error()'s text and returns `code` (rt_host.cpp)
-int rt_fail(int code, const char *fmt, ...);
 extern "C" int rtk_launch_encode(const void *accum, void *out, uint64_t n, uint32_t pow_mode, hipStream_t stream);
 extern "C" int rtk_launch_assemble(const void *src, uint64_t rank_stride, void *dst, uint32_t width, uint32_t height,
                                    uint32_t elem, uint32_t band_rows, uint32_t band_count, hipStream_t stream);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "rt_kernel.h"
+#include "rt_pack.h"
 #include "rt_trace.h"
 
 #define MHIP(expr)                                                                              \

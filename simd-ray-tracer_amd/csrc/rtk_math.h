@@ -17,7 +17,7 @@ namespace rtk {
 
 constexpr float kEps = 1e-4f;   // base.h:889 F32Epsilon
 constexpr float kFMax = 1e30f;  // base.h:891 F32Max
-constexpr float kPfDirTol = 1.0f / 65536.0f;  // |1 - |D|^2| bound of the secondary prefilter (host: rt_host.cpp)
+constexpr float kPfDirTol = 1.0f / 65536.0f;  // |1 - |D|^2| bound of the secondary prefilter (host: rt_pack.cpp)
 // RandomFloat's (Max-Min)/(f64)(u32)-1 rounded to f32 (base.h:985), for the
 // three ranges the path uses: (-0.5,0.5) and (0,1) -> 1, (-1,1) -> 2.
 constexpr float kInvRange1 = (float)(1.0 / 4294967295.0);
@@ -186,7 +186,7 @@ __device__ __forceinline__ uint32_t rgba8(float x, float y, float z, bool pw) {
 }
 
 // r0 = ((1 - eta)/(1 + eta))^2 comes from the sphere record: the host's IEEE
-// division and product per material and side (rt_host.cpp put_material), the
+// division and product per material and side (rt_pack.cpp put_material), the
 // same bits as the kernel's own (RTWeekend +0.4 %, its 8-rank share +1.3 %,
 // profiles/r06s_diel_tab_ab.txt)
 __device__ __forceinline__ float reflectance(float cos_t, float r0) {  // main.cpp:292-300

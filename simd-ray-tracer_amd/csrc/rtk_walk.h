@@ -178,8 +178,8 @@ __device__ __forceinline__ f2 pair_prefilter(const RayPk &r, f2 sx, f2 sy, f2 sz
     return e;
 }
 
-// The expanded prefilter of the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4; rt_host.cpp
-// cluster_table, "expanded", proves it): the same estimate written as dot products of the centre
+// The expanded prefilter of the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4; rt_pack.cpp
+// expand_table proves it): the same estimate written as dot products of the centre
 // itself, so the three packed subtractions C = S - O per pair go and nothing is left per sphere but
 // FMAs -- 7 packed ops instead of 10, the centre rows still in SGPRs.  With S' = RN(S - c0) from the
 // host's second table and O' = RN(O - c0) (c0: the table's centre, so that the values that cancel
@@ -332,7 +332,7 @@ __device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4
     }
 }
 
-// The clustered prefilter (secondary rays; rt_host.cpp cluster_table proves
+// The clustered prefilter (secondary rays; rt_pack.cpp cluster_table proves
 // it).  A wave tests the ray against about sqrt(n) cluster bounding volumes,
 // two per packed prefilter, and only the members of a cluster some lane may
 // reach run the per-sphere prefilter; a sphere pair some lane may hit sets
@@ -344,7 +344,7 @@ __device__ __forceinline__ void all_groups_smem(const TraceArgs &a, const float4
 // own estimate cleared the pair has a proven miss there, which its exact test
 // reproduces, so no per-lane flags are needed.
 constexpr int kClWords = 4;  // pair-mask words (n_groups <= 128)
-// Per-lane thresholds (pf_relative, rt_host.cpp cluster_table "relative"):
+// Per-lane thresholds (pf_relative, rt_pack.cpp per_lane_bounds):
 // cluster: e_c >= RN(cc kClRel + R_c); sphere: e >= RN(cc kPfRel + r^2) (kPfRel
 // below); behind: T < RN(b - cc kBehindRel).
 constexpr float kClRel = 9.2e-4f;               // >= (a + a^2 + E1)(1 + 6u), a = 8.917e-4
@@ -527,8 +527,8 @@ __device__ __forceinline__ void cluster_slab(f2 cc, f2 T, const RayPk &ray, cons
           [T] "v"(T), [ymid] "s"(ymid));
 }
 
-// The sphere a secondary ray leaves (scene-wide tables; rt_host.cpp cluster_table proves it, "own
-// sphere").  The ray's origin lies on sphere j, so the near-line estimate always flags j and the
+// The sphere a secondary ray leaves (scene-wide tables; rt_pack.cpp own_sphere_rho proves
+// it).  The ray's origin lies on sphere j, so the near-line estimate always flags j and the
 // behind rule never clears it (T >= -r against b < -r), yet the candidate is rejected: T - X < eps
 // turns it into T + X ~ 0.  A lane proves that for itself from the ray it has: with C = RN(S_j - O)
 // (the reference's own C_j, bit for bit), cc = |C|^2 and T = C.D as pair_prefilter forms them,
@@ -668,12 +668,12 @@ __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const 
 // clusters entered (two-level tables).
 // Tables of two or more mask words (more than 32 groups) have two levels: a
 // top cluster's entry ranges index sub-cluster entries of a few spheres each,
-// whose ranges index the member entries (rt_host.cpp cluster_table); the bound
+// whose ranges index the member entries (rt_pack.cpp lay_out); the bound
 // of a cluster covers every sphere under it, so a skipped top cluster skips
 // its sub-clusters' members too.
 // X: the walk-specialised scene-wide kernels' expanded prefilter (pair_prefilter_x): a.clusters is then
-// the recentred table, whose first row holds its centre c0, in front of entry 0 (rt_host.cpp cluster_table,
-// "expanded"; rt_kernel.h kPrefilterExpanded is the launch fact).
+// the recentred table, whose first row holds its centre c0, in front of entry 0 (rt_pack.cpp expand_table;
+// rt_kernel.h kPrefilterExpanded is the launch fact).
 template <bool SIMD, int W, bool GS, bool REL, bool X = false>
 __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float4 *lds_groups, const RayPk &ray,
                                                  Hit &h, bool fast, uint32_t own, PfStats *ps) {
@@ -683,7 +683,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
     uint64_t wave[kClWords] = {0ull, 0ull, 0ull, 0ull};
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
     constexpr bool kTwoLevels = W >= 2;
-    // per-lane part of the height-slab margin (REL tables; rt_host.cpp cluster_table)
+    // per-lane part of the height-slab margin (REL tables; rt_pack.cpp per_lane_bounds)
     const float oy = ray.y.x, dy = ray.y.y;
     const float slab_e0 = REL ? __builtin_fmaf(__builtin_fabsf(oy), 0x1p-21f, kSlabRel) : 0.0f;
     ClConst k;

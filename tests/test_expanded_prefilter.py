@@ -1,5 +1,5 @@
 """CPU property test of the expanded prefilter of the scene-wide cluster walks (DESIGN.md §3,
-"the expanded prefilter"; rtk_walk.h pair_prefilter_x; rt_host.cpp cluster_table, "Expanded").
+"the expanded prefilter"; rtk_walk.h pair_prefilter_x; rt_pack.cpp expand_table).
 
 The walk-specialised kernels test a cluster or member pair in 7 packed FMAs on the recentred table
 of rt_scene_clusters_expanded: with S' from the table and O' = RN(O - c0),

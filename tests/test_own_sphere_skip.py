@@ -22,7 +22,7 @@ from test_prefilter_bound import could_accept, fma, slot_spheres, unit
 F = np.float32
 OWN_CC = F(1.0 - 5.0 * 2.0 ** -18)  # rtk_walk.h kOwnCc
 OWN_LAM = F(1.9e-4)                 # rtk_walk.h kOwnLam
-R2_MIN, R2_MAX = F(2.6e-6), F(256.0)  # rt_host.cpp kOwnR2Min / kOwnR2Max
+R2_MIN, R2_MAX = F(2.6e-6), F(256.0)  # rt_pack.cpp kOwnR2Min / kOwnR2Max
 EPS = F(1e-4)
 
 

@@ -42,7 +42,7 @@ PF_REL = F(2.0 ** -15)  # rtk_walk.h kPfRel
 
 CL_REL = F(9.2e-4)            # rtk_walk.h kClRel
 BEHIND_REL = F(4.5 * 2.0 ** -24)  # rtk_walk.h kBehindRel
-SLAB_REL = F(2.0 ** -9)       # rt_kernel.h kSlabRel
+SLAB_REL = F(2.0 ** -9)       # rt_layout.h kSlabRel
 
 
 def slab_skip(tc, cc, oy, dy, srho, ymid, yhalf):
