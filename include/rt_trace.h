@@ -362,6 +362,52 @@ typedef struct rt_tile_work {
 int rt_trace_tile_work(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
                        const rt_tile_work *work, uint32_t n_work, uint64_t *d_rays, void *stream);
 
+/* How far the RGB bytes of one 32x32 reference tile (clipped to the image) moved. Alpha is not looked at. */
+typedef struct rt_tile_delta {
+    uint32_t Changed;    /* pixels with R, G or B different                       (<= 1024)        */
+    uint32_t MaxDelta;   /* largest |new - old| over the tile's R, G, B bytes     (<= 255)         */
+    uint32_t SumDelta;   /* sum of |new - old| over R, G, B of every pixel        (<= 783,360)     */
+    uint32_t SumSquares; /* sum of (new - old)^2 over the same                    (<= 199,756,800) */
+} rt_tile_delta;         /* 16 B */
+
+/* rt_trace_tile_work that also tells, per listed tile, how far this call moved the tile's displayed
+ * pixels: the decision half of an adaptive sampler (which tiles are still noisy, how many frames they
+ * want next), computed on the device by the pass that stores the RGBA8 bytes, 16 B per tile instead of
+ * an image copied to the host.  rt_trace_tile_work's whole contract holds -- the bits of both images,
+ * the ray count, what is refused, the launch key, the routing of uniform and mixed pairs,
+ * rt_trace_last_tile_counts, where the call may wait -- with one addition:
+ *  - d_delta: DEVICE array of rt_tile_count(Width, Height) entries, 16-byte aligned, indexed by Tile.
+ *    For every kept entry (Frames > 0), d_delta[Tile] receives the statistics of that tile's pixels
+ *    (clipped to the image) between "old", what CurrentImage held at the pixel before this call in
+ *    stream order, and "new", the RGBA8 this call stores there (RT_FLAG_SRGB_POW honoured).  The
+ *    pixels of dead (folded) block tiles are included: the same pass encodes them.
+ *  - Entries of tiles not listed, or listed with Frames == 0, are not written.  Nothing needs zeroing
+ *    beforehand.  Written asynchronously on `stream`, like the images.
+ *  - The caller owns the meaning of "old".  The library keeps no frame of its own: on a tile's first
+ *    round "old" is whatever the caller put into CurrentImage (a cleared image, the last frame shown,
+ *    uninitialised memory), and the first round's statistics measure the distance from that, not any
+ *    error.  Statistics are comparable from the second round of a tile on, where "old" is what the
+ *    previous round stored.
+ *  - d_delta == NULL or not 16-byte aligned: RT_EINVAL, before anything is enqueued or any key state
+ *    changes.  n_work == 0, or every entry at Frames == 0: RT_OK, nothing enqueued, nothing written.
+ *  - The statistics are no part of the launch key: the same tiles through rt_trace_tile_work,
+ *    rt_trace_tiles and this call share one key (CullPassRan 0 on the second of them).
+ *  - RGBA8 is stored by the closing pass at every launch shape (also where rt_trace_tile_work's
+ *    kernels would store it themselves: one frame, or rt_device_options EncodePass off); the bytes
+ *    are the same.  No buffer, staging or wait beyond rt_trace_tile_work's; rt_device_reserve covers it.
+ * The statistics are integers with no summation order: a given (old, new) pair of images has one result. */
+int rt_trace_tile_work_delta(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
+                             const rt_tile_work *work, uint32_t n_work, rt_tile_delta *d_delta,
+                             uint64_t *d_rays, void *stream);
+
+/* The same statistics between two RGBA8 images (DEVICE pointers, width x height u32 each), for every
+ * tile of the image: d_delta[Tile] for all rt_tile_count(width, height) tiles.  For a host that keeps
+ * two frames, as rt_on_render does.  Needs no rt_device and traces nothing; enqueued on `stream`
+ * (NULL: the null stream) of the current HIP device.  RT_EINVAL for a NULL pointer, a d_delta that is
+ * not 16-byte aligned, or an image for which rt_tile_count is 0. */
+int rt_tile_delta_rgba8(const uint32_t *d_old, const uint32_t *d_new, uint32_t width, uint32_t height,
+                        rt_tile_delta *d_delta, void *stream);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call

@@ -99,6 +99,14 @@ class RtTileWork(ctypes.Structure):  # rt_tile_work: one entry of rt_trace_tile_
     _fields_ = [("Tile", c_uint32), ("PreviousRayCount", c_uint32), ("Frames", c_uint32)]
 
 
+class RtTileDelta(ctypes.Structure):  # rt_tile_delta: one tile's RGBA8 change statistics, 16 B
+    _fields_ = [("Changed", c_uint32), ("MaxDelta", c_uint32), ("SumDelta", c_uint32), ("SumSquares", c_uint32)]
+
+
+# a copied-back rt_tile_delta array: np.frombuffer(bytes, tile_delta_dtype) or array.view(tile_delta_dtype)
+tile_delta_dtype = np.dtype([(n, "<u4") for n, _ in RtTileDelta._fields_])
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -178,6 +186,9 @@ SIGNATURES = {
                                c_void_p]),
     "rt_trace_tile_work": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
                                    c_void_p, c_void_p]),
+    "rt_trace_tile_work_delta": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
+                                         c_void_p, c_void_p, c_void_p]),
+    "rt_tile_delta_rgba8": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -531,13 +542,16 @@ class Device:
 
     def trace_tile_work(self, cam: RtCameraInfo, *, work, width: int, height: int, prev_ptr: int, cur_ptr: int,
                         rays_ptr: int, max_bounce: int = 5, simd: bool = True, band_rows: int = 32,
-                        accum_zero: bool = False, srgb_pow: bool = False, stream: Optional[int] = None) -> None:
+                        accum_zero: bool = False, srgb_pow: bool = False, stream: Optional[int] = None,
+                        delta_ptr: int = 0) -> None:
         """trace_tiles() with each tile's own counts in one launch (rt_trace_tile_work): `work` is a
         sequence of (tile, prev_count, frames) triples or an (n, 3) integer array; every listed tile
         folds `frames` frames from its own `prev_count`, an entry with frames == 0 is dropped, and no
         pixel outside the listed tiles is written.  The counts are no part of the launch key: the same
         tiles with other counts reuse the cull masks and the learned order.  The array is consumed
-        before the call returns."""
+        before the call returns.  A non-zero `delta_ptr` (rt_trace_tile_work_delta) is a device array of
+        tile_count(width, height) rt_tile_delta entries, 16-byte aligned: the entry of every listed tile
+        with frames > 0 receives how far the call moved the tile's RGBA8 pixels (tile_delta_dtype)."""
         w = tile_work_array(work)
         c = RtCameraInfo()
         ctypes.pointer(c)[0] = cam
@@ -545,6 +559,12 @@ class Device:
         c.PreviousImage = RtImage(prev_ptr, width, height, RT_FORMAT_R32B32G32A32_F32)
         d = RtTraceDesc(width, height, 0, 0, max_bounce, 1 if simd else 0, RT_SEED_PIXEL, band_rows, 1, 0,
                         (RT_FLAG_ACCUM_ZERO if accum_zero else 0) | (RT_FLAG_SRGB_POW if srgb_pow else 0))
+        if delta_ptr:
+            _check(lib().rt_trace_tile_work_delta(self.handle, ctypes.byref(c), ctypes.byref(d),
+                                                  c_void_p(w.ctypes.data if w.size else None), int(w.shape[0]),
+                                                  c_void_p(delta_ptr), c_void_p(rays_ptr), c_void_p(stream or 0)),
+                   "rt_trace_tile_work_delta")
+            return
         _check(lib().rt_trace_tile_work(self.handle, ctypes.byref(c), ctypes.byref(d),
                                         c_void_p(w.ctypes.data if w.size else None), int(w.shape[0]),
                                         c_void_p(rays_ptr), c_void_p(stream or 0)), "rt_trace_tile_work")
@@ -737,6 +757,15 @@ def encode_rgba8(accum_ptr: int, rgba8_ptr: int, n_pixels: int, srgb_pow: bool =
     """ColorFromV4(LinearToSRGB(v)) over a device-resident running mean (main.cpp:312-346)."""
     _check(lib().rt_encode_rgba8(c_void_p(accum_ptr), c_void_p(rgba8_ptr), n_pixels,
                                  RT_FLAG_SRGB_POW if srgb_pow else 0, c_void_p(stream or 0)), "rt_encode_rgba8")
+
+
+def tile_delta_rgba8(old_ptr: int, new_ptr: int, width: int, height: int, delta_ptr: int,
+                     stream: Optional[int] = None) -> None:
+    """rt_tile_delta_rgba8: per-tile change statistics between two device RGBA8 images (width x height
+    u32 each) into the device array `delta_ptr` (tile_count(width, height) rt_tile_delta entries,
+    16-byte aligned; view a copy with tile_delta_dtype).  Traces nothing."""
+    _check(lib().rt_tile_delta_rgba8(c_void_p(old_ptr), c_void_p(new_ptr), width, height, c_void_p(delta_ptr),
+                                     c_void_p(stream or 0)), "rt_tile_delta_rgba8")
 
 
 # ------------------------------------------------- OnInit / OnRender mirror

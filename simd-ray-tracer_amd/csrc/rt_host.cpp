@@ -733,8 +733,10 @@ static int check_trace_args(rt_device *d, const rt_camera_info *cam, const rt_tr
 // its own count.  desc then carries the LARGEST Frames of the list, by which the launch shape is chosen
 // (never more lanes than frames; 4 pixels per lane at one frame), and PreviousRayCount 0; the kernels
 // take each tile's pair from the table.  Nothing of the counts enters the key.
+// d_delta (rt_trace_tile_work_delta; needs sel): the RGBA8 image is left to the closing pass whatever the
+// launch shape, and that pass also writes each listed tile's change statistics.  No part of the key either.
 static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const TileSelection *sel,
-                        const TileCounts *counts, uint64_t *d_rays, void *stream) {
+                        const TileCounts *counts, uint64_t *d_rays, void *stream, rt_tile_delta *d_delta = nullptr) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (const int rc = check_trace_args(d, cam, desc, d_rays)) return rc;
     const uint32_t band_rows = desc->BandRows ? desc->BandRows : 32u;
@@ -1035,7 +1037,8 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     a.pix_perm = pixel_sort ? d->d_pix_perm : nullptr;
     a.pix_seg = d->pixel_seg;
     // (multi-frame launches only: a one-frame launch, OnRender's, keeps its store and one kernel fewer)
-    a.skip_cur = d->cur_pass && lpp >= 2 ? 1u : 0u;
+    // (the statistics need the old bytes: no kernel before the closing pass may store RGBA8, at any shape)
+    a.skip_cur = (d->cur_pass && lpp >= 2) || d_delta ? 1u : 0u;
     d->last.PixelsSorted = pixel_sort && !new_key && d->n_sorts > 0 ? 1u : 0u;
     d->last_n_tiles = n_selected;  // (SegmentsFolded: the dead tiles among these)
     d->last.TilesSelected = n_selected;
@@ -1106,10 +1109,12 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     // options EncodePass: the RGBA8 band image from the running mean the kernels stored (main.cpp:490's
     // store on its own, the same bits), written by one coalesced pass
     // (a tile list: over the listed tiles' pixels only, so no other RGBA8 pixel is written)
+    // (rt_trace_tile_work_delta: the same pass, one block per listed tile, with the tile's statistics)
     if (a.skip_cur && desc->Frames > 0 &&
-        (sel ? rtk_launch_encode_selected(&a, s)
-             : rtk_launch_encode(a.prev, a.cur, (uint64_t)local_rows * desc->Width, (a.flags & kFlagSrgbPow) ? 1u : 0u,
-                                 s)) != 0)
+        (d_delta ? rtk_launch_tile_delta_encode(&a, d_delta, s)
+         : sel   ? rtk_launch_encode_selected(&a, s)
+                 : rtk_launch_encode(a.prev, a.cur, (uint64_t)local_rows * desc->Width,
+                                     (a.flags & kFlagSrgbPow) ? 1u : 0u, s)) != 0)
         return fail(RT_EIO, "rt_trace: RGBA8 encode launch failed: %s", hipGetErrorString(hipGetLastError()));
     d->last.SplitHeadFrames = head_frames;
     return RT_OK;
@@ -1139,9 +1144,13 @@ extern "C" int rt_trace_tiles(rt_device *d, const rt_camera_info *cam, const rt_
     return trace_launch(d, cam, desc, &sel, nullptr, d_rays, stream);
 }
 
-extern "C" int rt_trace_tile_work(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc,
-                                  const rt_tile_work *work, uint32_t n_work, uint64_t *d_rays, void *stream) {
+// rt_trace_tile_work and rt_trace_tile_work_delta (want_delta: d_delta is required and receives the listed
+// tiles' change statistics from the closing RGBA8 pass).
+static int trace_tile_work(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const rt_tile_work *work,
+                           uint32_t n_work, bool want_delta, rt_tile_delta *d_delta, uint64_t *d_rays, void *stream) {
     if (!desc) return fail(RT_EINVAL, "rt_trace: NULL argument");
+    if (want_delta && (!d_delta || ((uintptr_t)d_delta & 15u)))
+        return fail(RT_EINVAL, "rt_trace_tile_work_delta: d_delta is %s", d_delta ? "not 16-byte aligned" : "NULL");
     rt_trace_desc dd = *desc;  // (desc's own PreviousRayCount / Frames are not read: every entry has its pair)
     dd.PreviousRayCount = 0;
     dd.Frames = 0;
@@ -1185,13 +1194,24 @@ extern "C" int rt_trace_tile_work(rt_device *d, const rt_camera_info *cam, const
     if (uniform) {  // one pair: rt_trace_tiles with it -- the same path, kernels and first-launch split
         dd.PreviousRayCount = first->PreviousRayCount;
         dd.Frames = first->Frames;
-        return trace_launch(d, cam, &dd, &sel, nullptr, d_rays, stream);
+        return trace_launch(d, cam, &dd, &sel, nullptr, d_rays, stream, d_delta);
     }
     dd.Frames = max_frames;  // (the launch shape's frames; PreviousRayCount stays 0: every tile has its own)
     TileCounts counts;
     counts.table = d->counts_table.data();
     counts.n_words = d->counts_table.size();
-    return trace_launch(d, cam, &dd, &sel, &counts, d_rays, stream);
+    return trace_launch(d, cam, &dd, &sel, &counts, d_rays, stream, d_delta);
+}
+
+extern "C" int rt_trace_tile_work(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc,
+                                  const rt_tile_work *work, uint32_t n_work, uint64_t *d_rays, void *stream) {
+    return trace_tile_work(d, cam, desc, work, n_work, false, nullptr, d_rays, stream);
+}
+
+extern "C" int rt_trace_tile_work_delta(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc,
+                                        const rt_tile_work *work, uint32_t n_work, rt_tile_delta *d_delta,
+                                        uint64_t *d_rays, void *stream) {
+    return trace_tile_work(d, cam, desc, work, n_work, true, d_delta, d_rays, stream);
 }
 
 extern "C" int rt_assemble_bands(const void *d_compact, uint64_t rank_stride_bytes, void *d_dst, uint32_t width,
@@ -1214,6 +1234,17 @@ extern "C" int rt_encode_rgba8(const float *d_accum_v4, uint32_t *d_rgba8, uint6
     if (flags & ~RT_FLAG_SRGB_POW) return fail(RT_EINVAL, "rt_encode_rgba8: unknown flags 0x%x", flags);
     if (rtk_launch_encode(d_accum_v4, d_rgba8, n_pixels, (flags & RT_FLAG_SRGB_POW) ? 1u : 0u, (hipStream_t)stream) != 0)
         return fail(RT_EIO, "rt_encode_rgba8: launch failed");
+    return RT_OK;
+}
+
+extern "C" int rt_tile_delta_rgba8(const uint32_t *d_old, const uint32_t *d_new, uint32_t width, uint32_t height,
+                                   rt_tile_delta *d_delta, void *stream) {
+    if (!d_old || !d_new || !d_delta) return fail(RT_EINVAL, "rt_tile_delta_rgba8: NULL buffer");
+    if ((uintptr_t)d_delta & 15u) return fail(RT_EINVAL, "rt_tile_delta_rgba8: d_delta is not 16-byte aligned");
+    if (rt_tile_count(width, height, nullptr) == 0u)
+        return fail(RT_EINVAL, "rt_tile_delta_rgba8: bad image size %ux%u", width, height);
+    if (rtk_launch_tile_delta(d_old, d_new, width, height, d_delta, (hipStream_t)stream) != 0)
+        return fail(RT_EIO, "rt_tile_delta_rgba8: launch failed");
     return RT_OK;
 }
 

@@ -272,6 +272,14 @@ extern "C" int rtk_launch_select(const TraceArgs *a, int lanes_per_pixel, uint32
 // rtk_launch_encode over the pixels of the selected reference tiles of a full image
 // (a->prev -> a->cur, a->width x a->local_rows, a->sel set): no other RGBA8 pixel is written.
 extern "C" int rtk_launch_encode_selected(const TraceArgs *a, hipStream_t stream);
+// rtk_launch_encode_selected that also writes, per selected reference tile t, delta[t] = the rt_tile_delta
+// (rt_trace.h; 16 B, 16-byte aligned) between the RGBA8 a->cur held and the RGBA8 it stores there
+// (rt_trace_tile_work_delta; a->sel set; entries of unselected tiles are not written).
+extern "C" int rtk_launch_tile_delta_encode(const TraceArgs *a, void *delta, hipStream_t stream);
+// The same statistics between two RGBA8 images, for every reference tile of a width x height image;
+// nothing else is written (rt_tile_delta_rgba8).
+extern "C" int rtk_launch_tile_delta(const uint32_t *old_img, const uint32_t *new_img, uint32_t width, uint32_t height,
+                                     void *delta, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

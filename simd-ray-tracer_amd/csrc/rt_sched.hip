@@ -1,6 +1,6 @@
 // rt_sched.hip — the kernels around the trace launch: the primary-ray cull
 // pass, dead-tile fold, primary group rows, pixel sort, heaviest-first tile
-// sort, XCD grouping, RGBA8 encode, ray-counter sum and band assembly, with
+// sort, XCD grouping, RGBA8 encode, per-tile RGBA8 change statistics, ray-counter sum and band assembly, with
 // their launchers and the tile geometry queries.  A launch over a list of
 // reference tiles (rt_trace_tiles, TraceArgs.sel) is decided here alone.
 #include <hip/hip_runtime.h>
@@ -849,6 +849,128 @@ extern "C" int rtk_launch_encode_selected(const TraceArgs *a, hipStream_t stream
     hipLaunchKernelGGL(rtk::encode_selected_kernel, dim3((a->width + 255u) / 256u, a->local_rows), dim3(256), 0, stream,
                        (const float4 *)a->prev, a->cur, a->width, a->sel, a->sel_tiles_x,
                        (a->flags & kFlagSrgbPow) ? 1u : 0u);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+namespace rtk {
+// One pixel's share of a tile's rt_tile_delta (rt_trace.h): alpha masked out of both words, then
+// v_sad_u8 sums the three byte differences in one op; a byte lane alone under the same op is that
+// channel's |new - old| (the other lanes are zero), for the maximum and the squares.
+__device__ __forceinline__ void delta_pixel(uint32_t o, uint32_t n, uint32_t &changed, uint32_t &mx, uint32_t &sum,
+                                            uint32_t &sq) {
+    o &= 0x00FFFFFFu;
+    n &= 0x00FFFFFFu;
+    changed += o != n ? 1u : 0u;
+    sum = __builtin_amdgcn_sad_u8(o, n, sum);
+    const uint32_t d0 = __builtin_amdgcn_sad_u8(o & 0xFFu, n & 0xFFu, 0u);
+    const uint32_t d1 = __builtin_amdgcn_sad_u8(o & 0xFF00u, n & 0xFF00u, 0u);
+    const uint32_t d2 = __builtin_amdgcn_sad_u8(o & 0xFF0000u, n & 0xFF0000u, 0u);
+    mx = max(mx, max(d0, max(d1, d2)));
+    sq += d0 * d0 + d1 * d1 + d2 * d2;
+}
+
+// Per-tile RGBA8 change statistics (rt_tile_delta: {Changed, MaxDelta, SumDelta, SumSquares} over the
+// R, G, B bytes), one 256-thread block per reference tile of a width x height image, grid (TilesX,
+// TilesY); thread t owns row t >> 3 of the tile and the four pixels at columns 4 (t & 7) ..+3, so a
+// wave covers 8 tile rows and a lane 16 contiguous RGBA8 bytes (64 of the running mean).
+//   ENCODE: the closing pass of rt_trace_tile_work_delta in place of encode_selected_kernel -- "new"
+//           is rgba8() of the running mean (the same function, the same bytes), "old" what old_img
+//           (== new_img, CurrentImage) held, read before the new bytes are stored there.
+//   else:   old_img against new_img, nothing stored (rt_tile_delta_rgba8).
+// A block whose bit of `sel` is clear (sel != NULL) leaves before any vector memory access: a uniform
+// branch on a scalar load.  vec (launch-uniform: width % 4 == 0 and 16-byte aligned RGBA8 bases): one
+// 16-byte access per lane and image, else four dwords.  Pixels outside the image are neither read nor
+// written and add nothing.  Integers only: lanes fold by __shfl_xor, the four waves through 64 B of
+// LDS, and one lane stores the tile's entry with one 16-byte store -- no atomics, nothing pre-zeroed,
+// no summation order to speak of.
+template <bool ENCODE>
+__global__ __launch_bounds__(256) void tile_delta_kernel(const float4 *accum, const uint32_t *old_img,
+                                                         uint32_t *new_img, uint32_t width, uint32_t height,
+                                                         const uint32_t *sel, uint32_t pw, uint32_t vec,
+                                                         uint4 *delta) {
+    __shared__ uint4 part[4];
+    const uint32_t tile = blockIdx.y * gridDim.x + blockIdx.x;
+    if (sel && !((sel[tile >> 5] >> (tile & 31u)) & 1u)) return;
+    const uint32_t t = threadIdx.x;
+    const uint32_t x = blockIdx.x * kRefTile + 4u * (t & 7u), y = blockIdx.y * kRefTile + (t >> 3);
+    const uint32_t npix = y < height && x < width ? min(4u, width - x) : 0u;  // (vec: 0 or 4)
+    const size_t pix = (size_t)y * width + x;
+    // (a pixel outside the image is never seen: it adds nothing)
+    uint32_t changed = 0, mx = 0, sum = 0, sq = 0;
+    if (npix && vec) {  // (four pixels: every load is issued before the first use)
+        const uint4 ov = *reinterpret_cast<const uint4 *>(old_img + pix);
+        uint4 nv;
+        if (ENCODE) {
+            float4 v[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) v[k] = accum[pix + k];
+            nv.x = rgba8(v[0].x, v[0].y, v[0].z, pw != 0u);
+            nv.y = rgba8(v[1].x, v[1].y, v[1].z, pw != 0u);
+            nv.z = rgba8(v[2].x, v[2].y, v[2].z, pw != 0u);
+            nv.w = rgba8(v[3].x, v[3].y, v[3].z, pw != 0u);
+            *reinterpret_cast<uint4 *>(new_img + pix) = nv;
+        } else {
+            nv = *reinterpret_cast<const uint4 *>(new_img + pix);
+        }
+        delta_pixel(ov.x, nv.x, changed, mx, sum, sq);
+        delta_pixel(ov.y, nv.y, changed, mx, sum, sq);
+        delta_pixel(ov.z, nv.z, changed, mx, sum, sq);
+        delta_pixel(ov.w, nv.w, changed, mx, sum, sq);
+    } else {  // (a width off the 4-pixel grid or an unaligned image: pixel by pixel, dwords)
+#pragma nounroll
+        for (uint32_t k = 0; k < npix; ++k) {
+            const uint32_t o = old_img[pix + k];
+            uint32_t n;
+            if (ENCODE) {
+                const float4 v = accum[pix + k];
+                new_img[pix + k] = n = rgba8(v.x, v.y, v.z, pw != 0u);
+            } else {
+                n = new_img[pix + k];
+            }
+            delta_pixel(o, n, changed, mx, sum, sq);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {  // (every lane active)
+        changed += (uint32_t)__shfl_xor((int)changed, off);
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
+        sum += (uint32_t)__shfl_xor((int)sum, off);
+        sq += (uint32_t)__shfl_xor((int)sq, off);
+    }
+    if ((t & 63u) == 0u) part[t >> 6] = make_uint4(changed, mx, sum, sq);
+    __syncthreads();
+    if (t == 0u) {
+        uint4 r = part[0];
+        for (uint32_t w = 1; w < 4u; ++w) {
+            const uint4 p = part[w];
+            r.x += p.x;
+            r.y = max(r.y, p.y);
+            r.z += p.z;
+            r.w += p.w;
+        }
+        delta[tile] = r;
+    }
+}
+}  // namespace rtk
+
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0u; }
+
+extern "C" int rtk_launch_tile_delta_encode(const TraceArgs *a, void *delta, hipStream_t stream) {
+    if (!a->sel || !delta || a->width == 0 || a->local_rows == 0) return -1;
+    const dim3 grid(a->sel_tiles_x, (a->local_rows + kRefTile - 1u) / kRefTile);
+    hipLaunchKernelGGL(rtk::tile_delta_kernel<true>, grid, dim3(256), 0, stream, (const float4 *)a->prev,
+                       (const uint32_t *)a->cur, a->cur, a->width, a->local_rows, a->sel,
+                       (a->flags & kFlagSrgbPow) ? 1u : 0u, (a->width & 3u) == 0u && aligned16(a->cur) ? 1u : 0u,
+                       (uint4 *)delta);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int rtk_launch_tile_delta(const uint32_t *old_img, const uint32_t *new_img, uint32_t width, uint32_t height,
+                                     void *delta, hipStream_t stream) {
+    if (!old_img || !new_img || !delta || width == 0 || height == 0) return -1;
+    const dim3 grid((width + kRefTile - 1u) / kRefTile, (height + kRefTile - 1u) / kRefTile);
+    hipLaunchKernelGGL(rtk::tile_delta_kernel<false>, grid, dim3(256), 0, stream, (const float4 *)nullptr, old_img,
+                       const_cast<uint32_t *>(new_img), width, height, (const uint32_t *)nullptr, 0u,
+                       (width & 3u) == 0u && aligned16(old_img) && aligned16(new_img) ? 1u : 0u, (uint4 *)delta);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
