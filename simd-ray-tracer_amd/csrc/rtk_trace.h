@@ -449,10 +449,10 @@ void trace_kernel(TraceArgs a) {
 
     st.post_end();
     // A mode-1 lane's pending hit: the accepted hit of the segment p still describes (its tmin, and
-    // the sphere index with the inside flag in bit 31), shaded at the start of the lane's next round.
+    // the winning class's key as it stands: the sphere index with the inside flag in bit 31, rtk_walk.h
+    // Hit), shaded at the start of the lane's next round.
     // Read only in mode 1 and written on every way into it, so a lane that finishes a sample (or a
     // Q > 1 lane moving to its next pixel slot) carries none over.
-    constexpr uint32_t kPendInside = 0x80000000u;
     float pend_t = 0.0f;
     uint32_t pend_s = 0u;
     // Re-derive the winner's HitNormal / NextRayOrigin exactly as they were
@@ -652,7 +652,7 @@ void trace_kernel(TraceArgs a) {
                 // rounds hold one kind, so the choice is the round's own; merged rounds hold both.
                 uint32_t own = kOwnNone;  // (lives for this round only: pend_s is dead once shaded)
                 if (kMergeable ? mode == 1u : do_sec != 0u)
-                    own = shade_hit(pend_t, pend_s & ~kPendInside, (pend_s & kPendInside) != 0u);
+                    own = shade_hit(pend_t, pend_s & ~kKeyInside, (pend_s & kKeyInside) != 0u);
                 else
                     start_sample(kernel_args(), x, y, a.prev_count + k, p);
                 bool done;
@@ -724,21 +724,25 @@ void trace_kernel(TraceArgs a) {
                         }
                     }
                     // ---- hit select (x64_math.h:579-585 HorizontalMin + first equal lane)
+                    // key: the winner's sphere index sidx with its inside flag in bit 31 (rtk_walk.h Hit), the
+                    // word a pending hit carries
                     float tmin;
-                    uint32_t sidx;
-                    bool inside;
+                    uint32_t key, sidx;
                     if (SIMD) {
-                        const float m02 = h.t0 < h.t2 ? h.t0 : h.t2;
-                        const float m13 = h.t1 < h.t3 ? h.t1 : h.t3;
-                        tmin = m02 < m13 ? m02 : m13;
-                        const uint32_t l = h.t0 == tmin ? 0u : h.t1 == tmin ? 1u : h.t2 == tmin ? 2u : 3u;
-                        const uint32_t gsel = l == 0 ? h.g0 : l == 1 ? h.g1 : l == 2 ? h.g2 : h.g3;
-                        sidx = gsel * 4u + l;
-                        inside = (h.ins >> l) & 1u;
+                        // Every t is kFMax or a finite value above kEps (candidate): never NaN, never a
+                        // zero of either sign, so the hardware minimum returns the bits the reference's
+                        // chain of < selects does.
+                        asm("v_min3_f32 %0, %1, %2, %3\n\t"
+                            "v_min_f32 %0, %0, %4"
+                            : "=&v"(tmin)
+                            : "v"(h.t0), "v"(h.t1), "v"(h.t2), "v"(h.t3));
+                        // the lowest class that holds the minimum: one select per class, no lane-masked region
+                        key = h.t0 == tmin ? h.k0 : h.t1 == tmin ? h.k1 : h.t2 == tmin ? h.k2 : h.k3;
+                        sidx = key & ~kKeyInside;
                     } else {
                         tmin = h.t0;
-                        sidx = h.g0;
-                        inside = h.ins != 0;
+                        sidx = h.k0;
+                        key = sidx | (h.ins != 0 ? kKeyInside : 0u);
                     }
                     if (tmin == kFMax) {
                         if (at_use(a.use_sky)) {  // main.cpp:434-438
@@ -759,7 +763,7 @@ void trace_kernel(TraceArgs a) {
                         done = true;
                     } else {
                         pend_t = tmin;
-                        pend_s = sidx | (inside ? kPendInside : 0u);
+                        pend_s = key;
                         done = false;
                     }
                 }

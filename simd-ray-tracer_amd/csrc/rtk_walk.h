@@ -69,16 +69,42 @@ __device__ __forceinline__ void sphere_core(const Sample &p, float sx, float sy,
 // Per-lane hit state.  SIMD rules: the reference's four lane minima
 // (MinT / MaterialIndex / InsideSphere, main.cpp:394-396), one per residue
 // class s & 3.  Scalar rules use slot 0 only (main.cpp:541-545).
+// A class keeps its sphere and its inside flag as one key, (4 g + L) | inside << 31: the word a
+// pending hit carries (trace_kernel pend_s), so the hit select picks one register per class and
+// rebuilds nothing.
+// The scalar rules keep what they kept: the sphere index in k0 and the flag, which is not sticky there,
+// in `ins` (the reference's two variables, main.cpp:574-575).  Their select is no more than an OR of
+// the two, so a packed key saves them nothing, and with it the 8-wave kernels of the scalar rules spilled
+// registers the parent form does not (profiles/r15a_resources.txt).  `ins` is dead under the SIMD rules.
+constexpr uint32_t kKeyInside = 0x80000000u;
 struct Hit {
     float t0, t1, t2, t3;
-    uint32_t g0, g1, g2, g3;
+    uint32_t k0, k1, k2, k3;
     uint32_t ins;
 };
 
 __device__ __forceinline__ void hit_reset(Hit &h) {
     h.t0 = h.t1 = h.t2 = h.t3 = kFMax;
-    h.g0 = h.g1 = h.g2 = h.g3 = 0;
+    h.k0 = h.k1 = h.k2 = h.k3 = 0;
     h.ins = 0;
+}
+
+// The key of an accepted candidate: s | in << 31 for the wave-uniform sphere index s (below 2^31).
+// gfx950 reads one scalar register or literal per VALU instruction, the select's lane mask included,
+// so selecting between the two scalars s and s | 2^31 costs two copies into VGPRs first.  The select's
+// own source modifier sets the bit instead: a negated source of v_cndmask_b32 is the source with bit 31
+// flipped, bit for bit (no arithmetic, nothing canonicalised), so one copy of s and one select do it.
+// Small sphere indices are f32 denormals as bit patterns: that the modifier flips bit 31 and flushes
+// nothing was confirmed on gfx950 by the bit-exact GPU suite (tests/test_gpu_hit_key.py among it, sphere
+// indices from 0 up); a port to another target has to check it again.
+// in_mask: the lane mask of `in`, taken where `in` is compared (candidate), so that it is the compare's
+// own SGPR pair.  A ballot taken inside the accept region is rebuilt there with v_cndmask + v_cmp_ne,
+// two VALU per accepted candidate and a VGPR live into the region.  Only the bits of lanes active at
+// the select are read, and for those the mask taken outside holds the lane's own `in`.
+__device__ __forceinline__ uint32_t hit_key(uint32_t s, uint64_t in_mask) {
+    uint32_t key;
+    asm("v_cndmask_b32_e64 %0, %1, -%1, %2" : "=v"(key) : "v"(s), "s"(in_mask));
+    return key;
 }
 
 // Exact intersection of one candidate sphere (main.cpp:413-429 / 561-578),
@@ -91,20 +117,22 @@ __device__ __forceinline__ void candidate(Hit &h, uint32_t g, float T, float dis
     const float X = fast ? sqrt_rn(r2 - dist) : __builtin_sqrtf(r2 - dist);
     float it = T - X;
     const bool in = it < kEps;
+    const uint64_t in_mask = __builtin_amdgcn_ballot_w64(in);  // (see hit_key)
     if (in) it = T + X;
+    const uint32_t s = 4u * g + (uint32_t)L;  // (wave-uniform)
     if (SIMD) {
         float &tl = L == 0 ? h.t0 : L == 1 ? h.t1 : L == 2 ? h.t2 : h.t3;
-        uint32_t &gl = L == 0 ? h.g0 : L == 1 ? h.g1 : L == 2 ? h.g2 : h.g3;
+        uint32_t &kl = L == 0 ? h.k0 : L == 1 ? h.k1 : L == 2 ? h.k2 : h.k3;
         if (it < tl && it > kEps) {  // strict: the earliest group keeps a tie
             tl = it;
-            gl = g;
-            h.ins |= (in ? 1u : 0u) << L;  // sticky OR (main.cpp:425)
+            // the class's flag is a sticky OR (main.cpp:425): bit 31 of the old key stays
+            kl = (kl & kKeyInside) | hit_key(s, in_mask);
         }
     } else {
         if (!(it > h.t0) && !(it < kEps)) {  // the later sphere wins a tie
             h.t0 = it;
-            h.g0 = 4u * g + (uint32_t)L;
-            h.ins = in ? 1u : 0u;
+            h.k0 = s;
+            h.ins = in ? 1u : 0u;  // (not sticky: main.cpp:574)
         }
     }
 }
