@@ -64,7 +64,7 @@ struct TraceStats<true> {
     uint32_t pri_blocked = 0, pri_waitsec = 0, pri_done = 0;
     uint32_t sec_done = 0, sec_waitpri = 0, done_trips = 0, done_lanes = 0;
     uint32_t sec_exact = 0, sec_badlanes = 0, sec_zerodir = 0, pf_rounds = 0;
-    PfStats pf = {0, 0, 0, 0, 0};
+    PfStats pf = {0, 0, 0, 0, 0, 0, 0};
     uint64_t cyc_pri = 0, cyc_sec = 0, cyc_fold = 0, cyc_setup = 0, cyc_cull = 0, cyc_sync = 0, cyc_post = 0;
     uint64_t t_entry = 0, t_setup = 0, t_cull = 0, t_sync = 0, t_trip = 0, t_fold = 0;  // clock readings
 
@@ -134,6 +134,14 @@ struct TraceStats<true> {
     __device__ __forceinline__ uint32_t *sec_hit() { return on ? &sec_hit_groups : nullptr; }
     __device__ __forceinline__ void flush(unsigned long long *stats, uint32_t lane) {
         if (!on || lane != 0) return;
+        // rt_debug_stats has 32 slots and every one is taken: a -DRTK_STATS -DRTK_STATS_NEAR build reports the walk's
+        // near-entry counts in the slots of the exact rounds' two lane counts (sec_badlanes: pf_near_entries,
+        // member-pair entries with a near lane; sec_zerodir: cl_near_entries, the same of cluster-pair entries)
+#ifdef RTK_STATS_NEAR
+        const uint32_t s_bad = pf.near_entries, s_zero = pf.cl_near_entries;
+#else
+        const uint32_t s_bad = sec_badlanes, s_zero = sec_zerodir;
+#endif
         const struct { uint32_t slot; unsigned long long v; } out[] = {
             {kStatPriIters, pri_it}, {kStatPriLanes, pri_lanes}, {kStatSecIters, sec_it}, {kStatSecLanes, sec_lanes},
             {kStatPriGroups, groups}, {kStatSecHitGroups, sec_hit_groups}, {kStatSecSparseIters, sparse_it},
@@ -144,8 +152,8 @@ struct TraceStats<true> {
             {kStatPfPairs, pf.pairs}, {kStatClTopEntered, pf.cl_top_entered}, {kStatPfLanePairs, pf.lane_pairs},
             {kStatPriBlocked, pri_blocked}, {kStatPriWaitSec, pri_waitsec}, {kStatPriDone, pri_done},
             {kStatSecDone, sec_done}, {kStatSecWaitPri, sec_waitpri}, {kStatDoneTrips, done_trips},
-            {kStatDoneLaneTrips, done_lanes}, {kStatSecExact, sec_exact}, {kStatSecBadLanes, sec_badlanes},
-            {kStatSecZeroDir, sec_zerodir}};
+            {kStatDoneLaneTrips, done_lanes}, {kStatSecExact, sec_exact}, {kStatSecBadLanes, s_bad},
+            {kStatSecZeroDir, s_zero}};
         for (const auto &o : out) atomicAdd(stats + o.slot, o.v);
     }
 };

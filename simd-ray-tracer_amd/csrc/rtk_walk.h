@@ -312,6 +312,8 @@ __device__ __forceinline__ void prefilter_group(const Group &G, const RayPk &p, 
 // what each counts there)
 struct PfStats {
     uint32_t groups, cl_tested, pairs, cl_top_entered, lane_pairs;
+    // entries some lane is near on either half (near-line ballots n0 | n1 != 0): member-pair entries, cluster-pair entries
+    uint32_t near_entries, cl_near_entries;
 };
 
 // Group g for a secondary ray through the prefilter: one wave branch per
@@ -580,11 +582,23 @@ __device__ __forceinline__ uint32_t own_sphere(const Sample &p, float4 sc, uint3
 
 // own (scene-wide tables): the slot this lane's ray leaves and cannot accept (own_sphere), kOwnNone for none
 // X: the expanded prefilter on the recentred table (pair_prefilter_x; scene-wide tables only)
+// Lazy flags (scene-wide tables): an entry's load, prefilter and two near-line ballots n0, n1 run on every
+// entry; the behind compares, the own-sphere compares and the merge only where some lane is near one of the
+// two spheres, under one wave-uniform branch on n0 | n1 (any_lane).  58 % of C2's member-pair entries and
+// 52 % of C5's have no near lane (profiles/r16a_near_share.txt) and then issue 2 v_cmp and the branch where
+// they issued 6 v_cmp and the merge's 8 scalar instructions.
+// Bit for bit the walk that runs all of it on every entry: member m's contribution to the wave mask is
+// (n_m & k_m & x_m) != 0 ? bits_m : 0 with n, k, x the near, not-behind and not-own lane masks.  Where n0 == 0 and n1 == 0 both conjunctions
+// are 0 whatever k and x are, so the skipped entry ORs nothing into the mask; where the branch is taken the
+// code is the unconditional one.  The mask is the same, so the recheck walks the same pairs in the same order.
+// Per-lane (REL) tables run the loop without the branch: their members test neither rule, the four-word form's
+// f0 | f1 region is this branch already, and no measured workload runs the one- and two-word forms.
 template <int W, bool REL, bool X>
 __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_t count, const RayPk &ray, const RayX &rx,
                                              uint64_t (&wave)[kClWords], const ClConst &k, uint32_t own, PfStats *ps) {
     static_assert(!(X && REL), "the expanded prefilter is for scene-wide tables");
     constexpr uint32_t kEntryBytes = 16u * cl_entry_f4(W, REL);
+    constexpr bool kLazy = !REL;
     if (ps) ps->groups += count;
     // (the end offset opaque to the optimiser: it otherwise derives a trip count and runs a
     // second, down-counting induction variable beside the offset -- one more SALU per entry)
@@ -608,6 +622,10 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
         // Either way a skipped pair is a proven miss.
         constexpr bool kBehind = !REL;
         const uint64_t n0m = __builtin_amdgcn_ballot_w64(!(v.x >= t0)), n1m = __builtin_amdgcn_ballot_w64(!(v.y >= t1));
+        if (ps) ps->near_entries += (n0m | n1m) != 0 ? 1u : 0u;
+        if constexpr (kLazy) {
+            if (!any_lane(n0m, n1m)) continue;
+        }
         if constexpr (W == 1) {
             const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
             const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
@@ -667,16 +685,19 @@ __device__ __forceinline__ void member_pairs(cv4f_t *ct, uint32_t first, uint32_
 // (The sub-level slab and behind tests stay: without them RTWeekend -0.1 % and -3 %, profiles/r06n_slab_ab.txt.)
 template <bool REL, bool X>
 __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const RayX &rx, const ClConst &k, uint64_t &m0,
-                                             uint64_t &m1, v4f_t &ranges) {
+                                             uint64_t &m1, v4f_t &ranges, PfStats *ps) {
     const Rows4 rows = load_rows4(e);  // (one scalar load per entry; row 2 = the entry's ranges)
     const v4f_t r0 = rows.r0, r1 = rows.r1, r3 = rows.r3;
     ranges = rows.r2;
     f2 T, cc = {};
     const f2 v = X ? pair_prefilter_x(rx, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T)
                    : pair_prefilter(ray, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T, cc);
+    // (near: the entry's two near-line lane masks, for the diagnostic build's count alone -- the behind compares and the
+    // slab block stay on every entry: under a branch on the near masks C2 and RTWeekend both lost, DESIGN_HISTORY)
     if constexpr (REL) {
         f2 t, b;
         cluster_thr(cc, k, f2{r1.z, r1.w}, f2{r3.x, r3.y}, t, b);
+        if (ps) ps->cl_near_entries += (__ballot(!(v.x >= t.x)) | __ballot(!(v.y >= t.y))) != 0 ? 1u : 0u;
         m0 = ballot_and(!(v.x >= t.x), !(T.x < b.x));
         m1 = ballot_and(!(v.y >= t.y), !(T.y < b.y));
         const v4f_t r4 = e[4];
@@ -685,6 +706,7 @@ __device__ __forceinline__ void cluster_pair(cv4f_t *e, const RayPk &ray, const 
         m0 &= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(d.x) > thr.x));
         m1 &= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(d.y) > thr.y));
     } else {
+        if (ps) ps->cl_near_entries += (__ballot(!(v.x >= r1.z)) | __ballot(!(v.y >= r1.w))) != 0 ? 1u : 0u;
         m0 = ballot_and(!(v.x >= r1.z), !(T.x < r3.x));
         m1 = ballot_and(!(v.y >= r1.w), !(T.y < r3.y));
     }
@@ -735,7 +757,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
             cv4f_t *e = cl_entry(ct, off);
             uint64_t m0, m1;
             v4f_t r2;
-            cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2);
+            cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2, ps);
             members(r2, m0 != 0, m1 != 0);
         }
     };
@@ -748,7 +770,7 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
         cv4f_t *e = cl_entry(ct, off);
         uint64_t m0, m1;
         v4f_t r2;
-        cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2);
+        cluster_pair<REL, X>(e, ray, rx, k, m0, m1, r2, ps);
         if constexpr (kTwoLevels) {
             if (ps) ps->lane_pairs += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
             if (ps) ps->cl_top_entered += (m0 != 0 ? 1u : 0u) + (m1 != 0 ? 1u : 0u);
