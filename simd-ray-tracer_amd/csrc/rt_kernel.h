@@ -1,4 +1,4 @@
-// rt_kernel.h — launch contract between the C-ABI host (rt_host.cpp) and the
+// rt_kernel.h — launch contract between the C-ABI host (rt_host.cpp, its launch decisions rt_plan.cpp) and the
 // gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_trace_tc.hip, rt_sched.hip).  Internal; not part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,7 +48,7 @@ struct TraceArgs {
     // has not read the count back: the grid then covers every tile and blocks past the count exit.
     const unsigned long long *live_total;
     // one-wave kernels (solo): tile_order / tile_cost index WAVES (4 * block tile + quadrant),
-    // so the heaviest-first order ranks every wave on its own cost (rt_host.cpp unit_waves)
+    // so the heaviest-first order ranks every wave on its own cost (rt_plan.cpp plan_launch, LaunchPlan.unit_waves)
     uint32_t unit_waves;
     // optional (rt_device_options PixelSort): the block tile's pixels dealt to its four waves by cost,
     // cheapest first: pix_perm[64 * tile + NPIX * wave + pl] = the pixel's index in the
@@ -139,7 +139,7 @@ enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWa
 enum { kWalkMask = 0xFF, kWalkTileCounts = 0x100 };
 // The four-wave kernels exist with the flag for a scene in the LDS image read through the scalar cache
 // (the default four-wave device); a per-tile launch of any other four-wave device (SphereSourceLds,
-// SceneInHbm, a scene beyond the LDS image) runs the one-wave run-time kernel (rt_host.cpp).
+// SceneInHbm, a scene beyond the LDS image) runs the one-wave run-time kernel (rt_plan.cpp route_kernel).
 static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { return scene_in_lds != 0u && src == kSrcSmem; }
 
 // ---- Routing of the walk-specialised one-wave kernels (trace_kernel<..., SOLO = true, WALK != kWalkAny>).
@@ -155,7 +155,7 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 //                   launch is empty)
 //   cluster walks   run only with a non-empty table over a non-empty scene: clusters set,
 //                   n_cpairs >= 1, n_groups >= 1 (their top loop has no zero-trip test), and with the
-//                   prefilter on (they do not test it; rt_trace sets clusters only with it)
+//                   prefilter on (they do not test it; plan_launch sets clusters only with it)
 //   expanded table  the scene-wide cluster walks (kWalkCl1 / Cl2 / Cl4) hold the expanded prefilter alone:
 //                   they run only where `clusters` is the expanded table (prefilter == kPrefilterExpanded:
 //                   it exists, every value of it is finite, and its extra slack G stays within a quarter
@@ -165,7 +165,7 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 // and the kernels exist only for the culled production shapes (rtk_walk_shape).  Every other launch
 // runs the run-time kernel (kWalkAny), which tests each fact where it matters and dispatches the
 // walk the table asks for.
-// The walk rt_trace asks for (TraceArgs.walk, rt_trace_info.Walk) of a one-wave launch, from the
+// The walk a launch asks for (rt_plan.cpp route_kernel; TraceArgs.walk, rt_trace_info.Walk) of a one-wave launch, from the
 // scene's table and the facts the host decides by; walk_any: rt_device_options WalkAny.
 static inline uint32_t rtk_walk_request(const TraceArgs &a, bool walk_any) {
     if (walk_any || !a.fast_sqrt || a.max_bounce == 0u) return kWalkAny;
@@ -191,7 +191,7 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
     // (and the expanded table is read by no other kernel: the host decides with rtk_walk_expanded)
     return a.walk <= (uint32_t)kWalkCl4Rel ? a.walk : (uint32_t)kWalkAny;
 }
-// Whether the launch's kernel walks the expanded table: rt_trace offers it (clusters = the expanded
+// Whether the launch's kernel walks the expanded table: route_kernel (rt_plan.cpp) offers it (clusters = the expanded
 // table, prefilter = kPrefilterExpanded), asks this, and puts the plain table back where the answer is no.
 static inline bool rtk_walk_expanded(const TraceArgs &a, int cull, int lanes_per_pixel) {
     const uint32_t k = rtk_walk_kernel(a, cull, lanes_per_pixel);
@@ -246,6 +246,7 @@ extern "C" int rtk_launch_tile_sort(uint32_t *cost, uint32_t *order, uint32_t *s
 extern "C" int rtk_launch_xcd_group(const uint32_t *order_in, uint32_t *order_out, uint32_t n_units,
                                     const unsigned long long *live_tiles, uint32_t *scratch, uint32_t *aux,
                                     hipStream_t stream);
+// (host arithmetic on the launch shapes of rtk_shape.h: defined in rt_plan.cpp)
 extern "C" uint32_t rtk_tile_count(uint32_t width, uint32_t local_rows, int lanes_per_pixel);
 extern "C" uint32_t rtk_tiles_x(uint32_t width, int lanes_per_pixel);
 // grid: blocks of the trace launch (tile_order[0..grid) when tile_order is set)

@@ -48,7 +48,7 @@ constexpr uint32_t cl_yhalf(uint32_t h) { return 18u + h; }
 constexpr uint32_t cl_bits(uint32_t word) { return 4u * (word == 0u ? kClRowBits0 : 3u + word); }
 constexpr float kSlabRel = 0x1p-9f;  // the slab test's per-lane margin per unit of cc (rt_pack.cpp cluster_bounds)
 constexpr uint32_t kClMaxGroups = 128;   // table built up to this many groups
-constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_host.cpp clusters_env; RTWeekend's
+constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_plan.h Switches.clusters; RTWeekend's
                                          // 121 groups: 11.3k Mrays/s clustered against 9.4k per group)
 
 // HBM layout of an uploaded scene (per rule set):

@@ -38,7 +38,7 @@ struct PackedSet {
     ClusterTable cl;
 };
 
-// pf_rel_env, cluster_k, sub_spheres: rt_device_options PrefilterRelative (-1 auto, 0 never, 1 always),
+// pf_rel_env, cluster_k, sub_spheres (rt_plan.h Switches): rt_device_options PrefilterRelative (-1 auto, 0 never, 1 always),
 // ClusterCount and SubClusterSpheres (0: per scene)
 int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env = -1, uint32_t cluster_k = 0,
              uint32_t sub_spheres = 0);

@@ -698,23 +698,7 @@ extern "C" int rtk_launch_xcd_group(const uint32_t *order_in, uint32_t *order_ou
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-extern "C" uint32_t rtk_tiles_x(uint32_t width, int lanes_per_pixel) {
-    return rtk_tile_count(width, 1u, lanes_per_pixel);
-}
-
-extern "C" uint32_t rtk_tile_count(uint32_t width, uint32_t local_rows, int lanes_per_pixel) {
-    uint32_t bw = 16u, bh = 16u;  // 2*TW x 2*TH of the launch's shape
-    switch (lanes_per_pixel) {
-        case 32: bw = 2u * rtk::Shape<32>::TW; bh = 2u * rtk::Shape<32>::TH; break;
-        case 16: bw = 2u * rtk::Shape<16>::TW; bh = 2u * rtk::Shape<16>::TH; break;
-        case 8: bw = 2u * rtk::Shape<8>::TW; bh = 2u * rtk::Shape<8>::TH; break;
-        case 4: bw = 2u * rtk::Shape<4>::TW; bh = 2u * rtk::Shape<4>::TH; break;
-        case 2: bw = 2u * rtk::Shape<2>::TW; bh = 2u * rtk::Shape<2>::TH; break;
-        case 0: bw = 2u * rtk::Shape<0>::TW; bh = 2u * rtk::Shape<0>::TH; break;
-        default: bw = 2u * rtk::Shape<1>::TW; bh = 2u * rtk::Shape<1>::TH; break;
-    }
-    return ((width + bw - 1u) / bw) * ((local_rows + bh - 1u) / bh);
-}
+// (rtk_tile_count and rtk_tiles_x, host arithmetic on the launch shapes: rt_plan.cpp)
 
 namespace rtk {
 // The primary rounds' group rows for this camera (TraceArgs.prim): one sphere
