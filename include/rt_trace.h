@@ -408,6 +408,87 @@ int rt_trace_tile_work_delta(rt_device *dev, const rt_camera_info *cam, const rt
 int rt_tile_delta_rgba8(const uint32_t *d_old, const uint32_t *d_new, uint32_t width, uint32_t height,
                         rt_tile_delta *d_delta, void *stream);
 
+/* one entry per tile of the image (rt_tile_count(Width, Height) entries, indexed by Tile), DEVICE memory */
+typedef struct rt_tile_counts {
+    uint32_t PreviousRayCount; /* frames already folded into this tile's pixels                   */
+    uint32_t Frames;           /* frames the tile wants folded by the next launch; 0: it rests    */
+} rt_tile_counts;              /* 8 B */
+
+/* rt_trace_tile_work_delta whose per-tile pairs live on the device: the refinement loop of an adaptive
+ * sampler enqueued on one stream with no host wait.  The host names the tiles that MAY be traced; the
+ * device table says, when the launch runs, how many frames each of them folds -- none, for a tile that
+ * rests.  rt_trace_tile_work_delta's contract holds with these differences:
+ *  - tiles: HOST array, the superset of tiles the call may trace.  Validated and keyed exactly as
+ *    rt_trace_tiles does it -- the same refusals, the same key -- so the key depends on nothing the
+ *    device holds: the same list again gives CullPassRan 0 whatever the table has become, tiles that came
+ *    to rest included, and the key is shared with rt_trace_tiles and with a mixed rt_trace_tile_work call
+ *    over the same tiles on this device.
+ *  - d_counts: DEVICE table of rt_tile_count(Width, Height) entries.  A listed tile takes its pair from
+ *    d_counts[Tile] at the moment the launch runs in stream order (write it on `stream` before the call:
+ *    rt_tile_counts_step below, a copy, the caller's own kernel).  The host never reads the table.
+ *    Entries of unlisted tiles are ignored, whatever they hold.
+ *  - A listed tile folds min(Frames, max_frames) frames from its PreviousRayCount; where PreviousRayCount
+ *    plus that many does not fit a u32 it folds 0 (the device cannot refuse an entry as the host does).
+ *  - A listed tile that folds 0 frames rests: no byte of either image is written for it, its d_delta
+ *    entry is not written, and it adds nothing to *d_rays or SegmentsFolded -- whether its block tiles
+ *    are live or dead.  With every listed tile at rest the call is RT_OK and writes nothing (launches are
+ *    still enqueued: the host does not know).  TilesSelected and TilesTraced count the listed tiles'
+ *    block tiles, resting ones included.
+ *  - max_frames, an upper bound of any entry's Frames, takes the place of "the LARGEST Frames of the
+ *    list" in the launch shape: the lanes per pixel never exceed it, and max_frames == 1 gives the
+ *    4-pixels-per-lane shape.  Keep it fixed over a loop: the shape is part of the key.
+ *    desc->PreviousRayCount and desc->Frames are not read.
+ *  - The call always routes as rt_trace_tile_work with mixed pairs does: no first-launch split, the
+ *    four-wave kernels only where that call has them, rt_trace_last_tile_counts 1, SegmentsFolded summed
+ *    on the device.
+ *  - d_delta: DEVICE, 16-byte aligned, as for rt_trace_tile_work_delta (entries of the tiles that folded
+ *    a frame are written), or NULL: no statistics, and RGBA8 is stored as rt_trace_tile_work stores it.
+ *  - RT_EINVAL, before anything is enqueued or any key state changes: d_counts == NULL, max_frames == 0,
+ *    d_delta neither NULL nor 16-byte aligned, and everything rt_trace_tiles refuses.  n_tiles == 0: RT_OK,
+ *    nothing enqueued.
+ *  - No pinned staging is used for the table: one small pass on `stream` copies the listed tiles' pairs,
+ *    clamped as above, into the library's own table.  The host waits only where rt_trace_tiles may wait
+ *    (a NEW list's bitmap upload); rt_device_reserve covers the call. */
+int rt_trace_tile_counts(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
+                         const uint32_t *tiles, uint32_t n_tiles, const rt_tile_counts *d_counts,
+                         uint32_t max_frames, rt_tile_delta *d_delta, uint64_t *d_rays, void *stream);
+
+/* The library's per-tile stopping rule, run on the device between two rt_trace_tile_counts calls. */
+typedef struct rt_tile_rule {
+    uint32_t Size;            /* sizeof(rt_tile_rule)                                             */
+    uint32_t MaxRoundFrames;  /* >= 1: the max_frames given to rt_trace_tile_counts               */
+    uint32_t MaxTileFrames;   /* >= 1: a tile rests once PreviousRayCount reaches it              */
+    uint32_t RestMaxDelta;    /* a tile rests when its round's MaxDelta <= this ...               */
+    uint32_t RestSumSquares;  /* ... and SumSquares <= this (0xFFFFFFFF: not looked at)           */
+} rt_tile_rule;
+typedef struct rt_tile_step_summary {
+    uint64_t NextFrames;      /* frames the next round folds, over all tiles                      */
+    uint32_t ActiveTiles;     /* tiles the next round traces                                      */
+    uint32_t RestedNow;       /* tiles this step put to rest                                      */
+} rt_tile_step_summary;       /* 16 B */
+
+/* Advances a device table by the round rt_trace_tile_counts(.., rule->MaxRoundFrames, d_delta, ..) just
+ * traced and decides each tile's next one.  Like rt_tile_delta_rgba8 it needs no rt_device and is
+ * enqueued on `stream` of the current HIP device.  For every tile of the width x height image, with f the
+ * frames its entry folded in that round (min(Frames, MaxRoundFrames), or 0 where the sum with
+ * PreviousRayCount does not fit a u32):
+ *  - f == 0: the entry is left as it is (a resting tile stays at rest until the caller wakes it).
+ *  - else done = PreviousRayCount + f, and the tile rests when done >= MaxTileFrames, or when
+ *    PreviousRayCount != 0 and its d_delta entry has MaxDelta <= RestMaxDelta and SumSquares <=
+ *    RestSumSquares (a tile's first round never rests on its statistics: they measure the distance from
+ *    whatever the caller had in CurrentImage).  The entry becomes {done, 0} at rest, else
+ *    {done, min(done, MaxRoundFrames, MaxTileFrames - done)}: as many frames again as the tile has.
+ *  - d_summary (DEVICE, or NULL): the sum of the new Frames of the entries this step advanced, how many
+ *    of them are > 0, and how many tiles it put to rest -- what the next round will do (entries left as
+ *    they are fold nothing then either).  Written, never accumulated: nothing needs zeroing, no atomics,
+ *    one value for a given input.  Copy its 16 B back asynchronously to learn when to stop.
+ * Tiles the trace call did not list must hold Frames == 0 (their d_delta entries were not written).
+ * RT_EINVAL for a NULL d_counts, d_delta or rule, a wrong Size, a zero MaxRoundFrames or MaxTileFrames, a
+ * d_delta that is not 16-byte aligned, or an image for which rt_tile_count is 0.  A caller's own kernel
+ * may write the table instead: this is the library's rule, not the only one. */
+int rt_tile_counts_step(rt_tile_counts *d_counts, const rt_tile_delta *d_delta, uint32_t width, uint32_t height,
+                        const rt_tile_rule *rule, rt_tile_step_summary *d_summary, void *stream);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call
@@ -463,7 +544,7 @@ typedef struct rt_trace_info {
                                  dead selected tiles' segments only             */
 } rt_trace_info;
 int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
-/* *out = 1 when the last launch on `dev` took per-tile counts (rt_trace_tile_work with mixed pairs),
+/* *out = 1 when the last launch on `dev` took per-tile counts (rt_trace_tile_work with mixed pairs, rt_trace_tile_counts),
  * 0 otherwise (rt_trace, rt_trace_tiles, a work list of one pair).  A query of its own: rt_trace_info keeps
  * the layout and the last field its callers know.  Host-side bookkeeping, never waits.  After such a
  * launch rt_trace_last_info's SegmentsFolded is summed on the device -- each dead block tile's in-image

@@ -107,6 +107,23 @@ class RtTileDelta(ctypes.Structure):  # rt_tile_delta: one tile's RGBA8 change s
 tile_delta_dtype = np.dtype([(n, "<u4") for n, _ in RtTileDelta._fields_])
 
 
+class RtTileCounts(ctypes.Structure):  # rt_tile_counts: one tile's entry of rt_trace_tile_counts' device table, 8 B
+    _fields_ = [("PreviousRayCount", c_uint32), ("Frames", c_uint32)]
+
+
+class RtTileRule(ctypes.Structure):  # rt_tile_rule: rt_tile_counts_step's stopping rule, 20 B
+    _fields_ = [(n, c_uint32) for n in ("Size", "MaxRoundFrames", "MaxTileFrames", "RestMaxDelta", "RestSumSquares")]
+
+
+class RtTileStepSummary(ctypes.Structure):  # rt_tile_step_summary: what rt_tile_counts_step decided, 16 B
+    _fields_ = [("NextFrames", c_uint64), ("ActiveTiles", c_uint32), ("RestedNow", c_uint32)]
+
+
+# a device table's host image: np.zeros(tile_count(w, h), tile_counts_dtype), or a (n, 2) uint32 array viewed so
+tile_counts_dtype = np.dtype([(n, "<u4") for n, _ in RtTileCounts._fields_])
+tile_step_summary_dtype = np.dtype([("NextFrames", "<u8"), ("ActiveTiles", "<u4"), ("RestedNow", "<u4")])
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -189,6 +206,9 @@ SIGNATURES = {
     "rt_trace_tile_work_delta": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
                                          c_void_p, c_void_p, c_void_p]),
     "rt_tile_delta_rgba8": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "rt_trace_tile_counts": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
+                                     c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "rt_tile_counts_step": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(RtTileRule), c_void_p, c_void_p]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -569,6 +589,34 @@ class Device:
                                         c_void_p(w.ctypes.data if w.size else None), int(w.shape[0]),
                                         c_void_p(rays_ptr), c_void_p(stream or 0)), "rt_trace_tile_work")
 
+    def trace_tile_counts(self, cam: RtCameraInfo, *, tiles, counts_ptr: int, max_frames: int, width: int, height: int,
+                          prev_ptr: int, cur_ptr: int, rays_ptr: int, delta_ptr: int = 0, max_bounce: int = 5,
+                          simd: bool = True, band_rows: int = 32, accum_zero: bool = False, srgb_pow: bool = False,
+                          stream: Optional[int] = None) -> None:
+        """trace_tile_work() whose pairs live on the device (rt_trace_tile_counts): `tiles` lists the tiles
+        that may be traced (the launch key, as trace_tiles), `counts_ptr` is a device table of
+        tile_count(width, height) rt_tile_counts entries (tile_counts_dtype) read when the launch runs in
+        stream order -- a listed tile folds min(Frames, max_frames) frames from its PreviousRayCount, and
+        rests, untouched, at 0 -- and a non-zero `delta_ptr` receives the statistics of the tiles that
+        folded a frame.  The host reads nothing back: a loop of this call and tile_counts_step() is
+        enqueued without a host wait."""
+        t = np.ascontiguousarray(np.asarray(list(tiles) if not isinstance(tiles, np.ndarray) else tiles).reshape(-1))
+        if t.size and (t.dtype.kind not in "iu" or int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+            raise ValueError("tiles: a sequence of tile indices (non-negative integers)")
+        if not 0 <= int(max_frames) <= 0xFFFFFFFF:
+            raise ValueError("max_frames: a u32")
+        t = t.astype(np.uint32)
+        c = RtCameraInfo()
+        ctypes.pointer(c)[0] = cam
+        c.CurrentImage = RtImage(cur_ptr, width, height, RT_FORMAT_R8G8B8A8_U32)
+        c.PreviousImage = RtImage(prev_ptr, width, height, RT_FORMAT_R32B32G32A32_F32)
+        d = RtTraceDesc(width, height, 0, 0, max_bounce, 1 if simd else 0, RT_SEED_PIXEL, band_rows, 1, 0,
+                        (RT_FLAG_ACCUM_ZERO if accum_zero else 0) | (RT_FLAG_SRGB_POW if srgb_pow else 0))
+        _check(lib().rt_trace_tile_counts(self.handle, ctypes.byref(c), ctypes.byref(d),
+                                          c_void_p(t.ctypes.data if t.size else None), int(t.size),
+                                          c_void_p(counts_ptr or None), int(max_frames), c_void_p(delta_ptr or None),
+                                          c_void_p(rays_ptr), c_void_p(stream or 0)), "rt_trace_tile_counts")
+
     def last_info(self) -> dict:
         """What the last trace launched (rt_trace_last_info): segments counted
         but folded analytically (dead tiles), P, tiles traced / total, whether
@@ -757,6 +805,24 @@ def encode_rgba8(accum_ptr: int, rgba8_ptr: int, n_pixels: int, srgb_pow: bool =
     """ColorFromV4(LinearToSRGB(v)) over a device-resident running mean (main.cpp:312-346)."""
     _check(lib().rt_encode_rgba8(c_void_p(accum_ptr), c_void_p(rgba8_ptr), n_pixels,
                                  RT_FLAG_SRGB_POW if srgb_pow else 0, c_void_p(stream or 0)), "rt_encode_rgba8")
+
+
+def tile_rule(max_round_frames: int, max_tile_frames: int, rest_max_delta: int = 0,
+              rest_sum_squares: int = 0xFFFFFFFF) -> RtTileRule:
+    """An rt_tile_rule with its Size set."""
+    return RtTileRule(ctypes.sizeof(RtTileRule), max_round_frames, max_tile_frames, rest_max_delta, rest_sum_squares)
+
+
+def tile_counts_step(counts_ptr: int, delta_ptr: int, width: int, height: int, rule: RtTileRule, summary_ptr: int = 0,
+                     stream: Optional[int] = None) -> None:
+    """rt_tile_counts_step: advances the device table `counts_ptr` (tile_count(width, height) rt_tile_counts
+    entries) by the round Device.trace_tile_counts(max_frames=rule.MaxRoundFrames, delta_ptr=...) just
+    traced and decides every tile's next one by `rule` (tile_rule()); a non-zero `summary_ptr` (16 B of
+    device memory, tile_step_summary_dtype) receives the next round's frames, active tiles and the tiles
+    put to rest.  Enqueued on `stream`; nothing is read back."""
+    _check(lib().rt_tile_counts_step(c_void_p(counts_ptr or None), c_void_p(delta_ptr or None), width, height,
+                                     ctypes.byref(rule), c_void_p(summary_ptr or None), c_void_p(stream or 0)),
+           "rt_tile_counts_step")
 
 
 def tile_delta_rgba8(old_ptr: int, new_ptr: int, width: int, height: int, delta_ptr: int,

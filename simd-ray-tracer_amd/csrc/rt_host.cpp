@@ -71,6 +71,8 @@ struct TileState {
 // (TraceArgs.tile_counts_at: two words per reference tile of the image) lies behind the bitmap in
 // d_sel (rt_kernel.h rtk_sel_table_at) and is uploaded on EVERY such call -- the counts are no part
 // of the key -- through two pinned slots of its own, by the same scheme
+// rt_trace_tile_counts: that table is written by a pass on the launch's stream from the caller's device table (no
+// staging), and behind it lies the bitmap of the listed tiles that fold a frame (rtk_sel_active_at), for the closing pass
 struct SelectionStaging {
     uint32_t *d_sel = nullptr;
     StagedWords bits, counts;
@@ -549,26 +551,35 @@ extern "C" int rt_device_reserve(rt_device *d, uint32_t width, uint32_t local_ro
 
 // ---- The trace launch, in stages (trace_launch, below, is their sequence).
 
-// A launch's per-tile counts (rt_trace_tile_work with mixed pairs): the table the kernels read
-// (rt_plan.h TileWorkList.table).
+// A launch's per-tile counts, by where they come from: none; a host table (rt_trace_tile_work with mixed
+// pairs: the table the kernels read, rt_plan.h TileWorkList.table, uploaded through the pinned slots); or
+// the caller's device table (rt_trace_tile_counts), from which a pass on the launch's stream builds the
+// kernels' table (rtk_launch_counts_table) -- the host never sees a count.
+enum CountsSource { kCountsNone = 0, kCountsHost, kCountsDevice };
 struct TileCounts {
-    const uint32_t *table = nullptr;
-    size_t n_words = 0;  // 2 x the image's reference tiles
+    CountsSource source = kCountsNone;
+    const uint32_t *table = nullptr;  // host: the table
+    size_t n_words = 0;               //       2 x the image's reference tiles
+    const rt_tile_counts *d_table = nullptr;  // device: the caller's table
+    uint32_t max_frames = 0;                  //         the bound its Frames are clamped to
 };
 
 // What a launch covers beyond rt_trace's every tile of the band.
 // sel (rt_trace_tiles): the listed reference tiles of the full image (one band, validated against
 // desc's image and not empty).
-// counts (rt_trace_tile_work with mixed pairs; needs sel): every listed tile folds its own frames from
-// its own count.  desc then carries the LARGEST Frames of the list, by which the launch shape is chosen
-// (never more lanes than frames; 4 pixels per lane at one frame), and PreviousRayCount 0; the kernels
-// take each tile's pair from the table.  Nothing of the counts enters the key.
+// counts (rt_trace_tile_work with mixed pairs, rt_trace_tile_counts; needs sel): every listed tile folds
+// its own frames from its own count.  desc then carries the LARGEST Frames of the list (a device table: the
+// caller's bound of them), by which the launch shape is chosen (never more lanes than frames; 4 pixels per
+// lane at one frame), and PreviousRayCount 0; the kernels take each tile's pair from the table.  Nothing of
+// the counts enters the key.  With a device table a listed tile may fold no frame: it rests (no byte of it
+// is written), and the closing pass takes the bitmap of the tiles that do not (rtk_sel_active_at).
 // d_delta (rt_trace_tile_work_delta; needs sel): the RGBA8 image is left to the closing pass whatever the
 // launch shape, and that pass also writes each listed tile's change statistics.  No part of the key either.
 struct LaunchRequest {
     const TileSelection *sel = nullptr;
-    const TileCounts *counts = nullptr;
+    TileCounts counts;
     rt_tile_delta *d_delta = nullptr;
+    bool per_tile() const { return counts.source != kCountsNone; }
 };
 
 // The camera and the descriptor into TraceArgs, with the device's scene and table pointers.
@@ -709,11 +720,17 @@ static LiveCounts live_counts(rt_device *d, const LaunchPlan &p, TraceArgs &a) {
 static int bind_launch(rt_device *d, const LaunchRequest &rq, const LaunchPlan &p, TraceArgs &a, hipStream_t s) {
     const TileState &t = d->tiles;
     a.tile_order = t.order_valid ? t.order : nullptr;
-    if (rq.counts) {  // this call's table, whatever the key: the counts are no part of it
-        a.tile_counts_at = rtk_sel_table_at(rq.sel->n_tiles);
-        if (const int rc = staged_upload(d->sel.counts, d->sel.d_sel + a.tile_counts_at, rq.counts->table,
-                                         rq.counts->n_words, s))
-            return rc;
+    if (rq.per_tile()) {  // this call's table, whatever the key: the counts are no part of it
+        const uint32_t n_ref = rq.sel->n_tiles;
+        a.tile_counts_at = rtk_sel_table_at(n_ref);
+        uint32_t *table = d->sel.d_sel + a.tile_counts_at;
+        if (rq.counts.source == kCountsHost) {
+            if (const int rc = staged_upload(d->sel.counts, table, rq.counts.table, rq.counts.n_words, s)) return rc;
+        } else if (rtk_launch_counts_table(rq.counts.d_table, d->sel.d_sel, n_ref, rq.counts.max_frames, table,
+                                           d->sel.d_sel + rtk_sel_active_at(n_ref), s) != 0) {
+            // (the key's bitmap is on the device by now: begin_key's upload, or an earlier call's)
+            return fail(RT_EIO, "rt_trace_tile_counts: table pass launch failed: %s", hipGetErrorString(hipGetLastError()));
+        }
     }
     // (the identity order knows no selection: both paths of begin_key leave a sorted order for a tile list)
     if (rq.sel && !a.tile_order) return fail(RT_EIO, "rt_trace_tiles: no tile order for the selection");
@@ -741,14 +758,14 @@ static void record_info(rt_device *d, const rt_trace_desc *desc, const LaunchReq
     l.info.GroupsPerRuleSet = a.n_groups;
     l.info.OneWaveGroups = a.solo;
     l.info.Walk = a.walk;
-    l.tile_counts = rq.counts != nullptr;
+    l.tile_counts = rq.per_tile();
     l.folded_on_device = false;
 }
 
 // The pixels of dead tiles, folded without tracing.
 static int fold_empty_tiles(rt_device *d, const LaunchRequest &rq, const LaunchPlan &p, const TraceArgs &a, hipStream_t s) {
     TileState &t = d->tiles;
-    if (!rq.counts) {
+    if (!rq.per_tile()) {
         if (rtk_launch_empty(&a, p.lpp, t.live, t.cull_counters + kCullTotals + 1, s) != 0)
             return fail(RT_EIO, "rt_trace: empty-tile launch failed: %s", hipGetErrorString(hipGetLastError()));
         return RT_OK;
@@ -818,8 +835,12 @@ static int run_parts(rt_device *d, const rt_trace_desc *desc, const LaunchReques
 // store on its own, the same bits), written by one coalesced pass
 // (a tile list: over the listed tiles' pixels only, so no other RGBA8 pixel is written)
 // (rt_trace_tile_work_delta: the same pass, one block per listed tile, with the tile's statistics)
-static int closing_pass(const rt_trace_desc *desc, const LaunchRequest &rq, const TraceArgs &a, hipStream_t s) {
-    if (!a.skip_cur || desc->Frames == 0) return RT_OK;
+// (rt_trace_tile_counts: over the listed tiles that folded a frame -- the table pass's bitmap in place of the key's)
+static int closing_pass(const rt_device *d, const rt_trace_desc *desc, const LaunchRequest &rq, const TraceArgs &launched,
+                        hipStream_t s) {
+    if (!launched.skip_cur || desc->Frames == 0) return RT_OK;
+    TraceArgs a = launched;
+    if (rq.counts.source == kCountsDevice) a.sel = d->sel.d_sel + rtk_sel_active_at(rq.sel->n_tiles);
     if ((rq.d_delta ? rtk_launch_tile_delta_encode(&a, rq.d_delta, s)
          : rq.sel   ? rtk_launch_encode_selected(&a, s)
                     : rtk_launch_encode(a.prev, a.cur, (uint64_t)a.local_rows * desc->Width,
@@ -828,7 +849,7 @@ static int closing_pass(const rt_trace_desc *desc, const LaunchRequest &rq, cons
     return RT_OK;
 }
 
-// rt_trace, rt_trace_tiles, rt_trace_tile_work and rt_trace_tile_work_delta behind their own checks.
+// rt_trace, rt_trace_tiles, rt_trace_tile_work, rt_trace_tile_work_delta and rt_trace_tile_counts behind their own checks.
 static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const LaunchRequest &rq,
                         uint64_t *d_rays, void *stream) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
@@ -842,7 +863,7 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
     TileState &t = d->tiles;
     TraceArgs a;
     fill_args(d, cam, desc, rs, local_rows, d_rays, a);
-    const LaunchPlan p = plan_launch(d->sw, d->facts[rs], rs, d->cu_count, *desc, local_rows, rq.sel, rq.counts != nullptr,
+    const LaunchPlan p = plan_launch(d->sw, d->facts[rs], rs, d->cu_count, *desc, local_rows, rq.sel, rq.per_tile(),
                                      rq.d_delta != nullptr, {d->scene[rs].clusters, d->scene[rs].clusters_x}, a, t.next_key);
     HIP_OK(hipSetDevice(d->ordinal));
     hipStream_t s = (hipStream_t)stream;  // NULL = the HIP null stream
@@ -861,12 +882,12 @@ static int trace_launch(rt_device *d, const rt_camera_info *cam, const rt_trace_
         if (const int rc = begin_key(d, rq, p, a, s)) return rc;
     // (a culled new key's launch may split; not with per-tile counts: a split would need a head per tile)
     const SplitSchedule split = split_schedule(desc->Frames, p.lanes, d->sw.head_samples, d->sw.split_parts, d->sw.split_growth,
-                                               new_key && p.cull && p.sched && d->sw.split && !rq.counts);
+                                               new_key && p.cull && p.sched && d->sw.split && !rq.per_tile());
     const LiveCounts live = live_counts(d, p, a);
     if (const int rc = bind_launch(d, rq, p, a, s)) return rc;
     record_info(d, desc, rq, p, a, new_key);
     if (const int rc = run_parts(d, desc, rq, p, split, live, a, s)) return rc;
-    if (const int rc = closing_pass(desc, rq, a, s)) return rc;
+    if (const int rc = closing_pass(d, desc, rq, a, s)) return rc;
     d->last.info.SplitHeadFrames = split.head_frames;
     return RT_OK;
 }
@@ -921,8 +942,9 @@ static int trace_tile_work(rt_device *d, const rt_camera_info *cam, const rt_tra
         return trace_launch(d, cam, &dd, rq, d_rays, stream);
     }
     dd.Frames = w.max_frames;  // (the launch shape's frames; PreviousRayCount stays 0: every tile has its own)
-    const TileCounts counts = {w.table.data(), w.table.size()};
-    rq.counts = &counts;
+    rq.counts.source = kCountsHost;
+    rq.counts.table = w.table.data();
+    rq.counts.n_words = w.table.size();
     return trace_launch(d, cam, &dd, rq, d_rays, stream);
 }
 
@@ -935,6 +957,36 @@ extern "C" int rt_trace_tile_work_delta(rt_device *d, const rt_camera_info *cam,
                                         const rt_tile_work *work, uint32_t n_work, rt_tile_delta *d_delta,
                                         uint64_t *d_rays, void *stream) {
     return trace_tile_work(d, cam, desc, work, n_work, true, d_delta, d_rays, stream);
+}
+
+extern "C" int rt_trace_tile_counts(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc,
+                                    const uint32_t *tiles, uint32_t n_tiles, const rt_tile_counts *d_counts,
+                                    uint32_t max_frames, rt_tile_delta *d_delta, uint64_t *d_rays, void *stream) {
+    // the device-free plan of the call (rt_plan.cpp): its refusals, the list's selection, the launch's desc.
+    // The list is consumed here (the bitmap lives in the device's own host vector), the table never read.
+    if (!d) return fail(RT_EINVAL, "rt_trace: NULL argument");
+    TileCountsCall call;
+    if (const int rc = plan_tile_counts(true, d->lut_set, d->scene_set, cam, desc, tiles, n_tiles, d_counts, max_frames,
+                                        d_delta, d_rays, d->sel.tile_bits, call))
+        return rc;
+    if (call.nothing) return RT_OK;
+    LaunchRequest rq;
+    rq.sel = &call.sel;
+    rq.d_delta = d_delta;
+    rq.counts.source = kCountsDevice;
+    rq.counts.d_table = d_counts;
+    rq.counts.max_frames = max_frames;
+    return trace_launch(d, cam, &call.desc, rq, d_rays, stream);
+}
+
+extern "C" int rt_tile_counts_step(rt_tile_counts *d_counts, const rt_tile_delta *d_delta, uint32_t width, uint32_t height,
+                                   const rt_tile_rule *rule, rt_tile_step_summary *d_summary, void *stream) {
+    uint32_t n_tiles = 0;
+    if (const int rc = check_tile_step(d_counts, d_delta, width, height, rule, &n_tiles)) return rc;
+    if (rtk_launch_tile_counts_step(d_counts, d_delta, n_tiles, rule->MaxRoundFrames, rule->MaxTileFrames,
+                                    rule->RestMaxDelta, rule->RestSumSquares, d_summary, (hipStream_t)stream) != 0)
+        return fail(RT_EIO, "rt_tile_counts_step: launch failed");
+    return RT_OK;
 }
 
 extern "C" int rt_assemble_bands(const void *d_compact, uint64_t rank_stride_bytes, void *d_dst, uint32_t width,

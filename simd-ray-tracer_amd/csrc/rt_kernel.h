@@ -92,8 +92,10 @@ struct TraceArgs {
     // rtk_tile_counts(a); 0 = none: the launch's prev_count / frames hold for every tile.  A block tile
     // lies in one reference tile, so a wave takes one pair: the trace kernels compiled with
     // kWalkTileCounts overwrite their by-value prev_count / frames with it before anything reads them,
-    // and rtk_launch_empty_counts folds each dead tile by its own pair.  Every listed tile's Frames is
-    // >= 1 (the host drops the others), and the launch's own frames field holds the largest of them.
+    // and rtk_launch_empty_counts folds each dead tile by its own pair.  In a host-built table every listed
+    // tile's Frames is >= 1 (the host drops the others); in a device-built one (rtk_launch_counts_table) a
+    // listed tile may hold 0 frames: it rests, and both kernels leave it before any store.  The launch's own
+    // frames field holds the largest Frames of the table, or a bound of them.
     // The table is named by its word offset from `sel` -- it lies behind the bitmap in the same device
     // buffer (rtk_sel_table_at) -- and not by a pointer of its own, because a u32 fits the struct's tail
     // padding: sizeof(TraceArgs) stays what it was, and with it the kernarg offsets of everything
@@ -107,9 +109,19 @@ static inline __host__ __device__ const uint32_t *rtk_tile_counts(const TraceArg
     return a.tile_counts_at ? a.sel + a.tile_counts_at : nullptr;
 }
 // the selection buffer of an image of n reference tiles: the bitmap's words, then (8-byte aligned) the
-// counts table's 2 n words
+// counts table's 2 n words, then (8-byte aligned again) a second bitmap of the same size: the listed
+// tiles that fold at least one frame in a launch whose table the device built (rtk_launch_counts_table)
 static inline uint32_t rtk_sel_table_at(uint32_t n_ref_tiles) { return 2u * ((n_ref_tiles + 63u) / 64u); }
-static inline size_t rtk_sel_buffer_words(uint32_t n_ref_tiles) { return rtk_sel_table_at(n_ref_tiles) + 2u * (size_t)n_ref_tiles; }
+static inline size_t rtk_sel_active_at(uint32_t n_ref_tiles) { return rtk_sel_table_at(n_ref_tiles) + 2u * (size_t)n_ref_tiles; }
+static inline size_t rtk_sel_buffer_words(uint32_t n_ref_tiles) { return rtk_sel_active_at(n_ref_tiles) + rtk_sel_table_at(n_ref_tiles); }
+// The frames a tile folds from a caller's device entry {prev, frames} in a launch of at most max_frames
+// (rt_trace_tile_counts, rt_tile_counts_step): the entry's frames clamped to the launch's, and 0 -- the
+// tile rests -- where prev + that many no longer fits the u32 frame count.  The device cannot refuse an
+// entry as the host refuses an rt_tile_work one, so an impossible entry folds nothing.
+static inline __host__ __device__ uint32_t rtk_effective_frames(uint32_t prev, uint32_t frames, uint32_t max_frames) {
+    const uint32_t f = frames < max_frames ? frames : max_frames;
+    return prev > 0xFFFFFFFFu - f ? 0u : f;
+}
 constexpr uint32_t kRefTile = 32;  // the reference's TileSize (main.cpp:9; RT_TILE_SIZE of rt_trace.h)
 // live[] values of a block tile (rtk_launch_cull / rtk_launch_select): dead (folded by rtk_launch_empty),
 // live (traced), or outside the launch's tile selection (neither: no byte of it is written)
@@ -281,6 +293,18 @@ extern "C" int rtk_launch_tile_delta_encode(const TraceArgs *a, void *delta, hip
 // nothing else is written (rt_tile_delta_rgba8).
 extern "C" int rtk_launch_tile_delta(const uint32_t *old_img, const uint32_t *new_img, uint32_t width, uint32_t height,
                                      void *delta, hipStream_t stream);
+// rt_trace_tile_counts' table pass: counts (the caller's DEVICE rt_tile_counts array, one entry per
+// reference tile) and the key's bitmap sel -> table (rtk_sel_table_at: {prev, rtk_effective_frames} for a
+// listed tile, {0, 0} for every other, whose entry is not read) and active (rtk_sel_active_at: the bitmap of
+// the listed tiles that fold a frame; the closing pass takes it for its selection, so a resting tile gets
+// no RGBA8 and no statistics).  All three lie in the selection buffer; read and written in stream order.
+extern "C" int rtk_launch_counts_table(const void *counts, const uint32_t *sel, uint32_t n_ref_tiles, uint32_t max_frames,
+                                       uint32_t *table, uint32_t *active, hipStream_t stream);
+// rt_tile_counts_step: the per-tile stopping rule over counts (rt_tile_counts) and delta (rt_tile_delta) of
+// n_ref_tiles tiles, one block; summary (rt_tile_step_summary, optional) is written, never accumulated.
+extern "C" int rtk_launch_tile_counts_step(void *counts, const void *delta, uint32_t n_ref_tiles, uint32_t max_round,
+                                           uint32_t max_tile, uint32_t rest_max_delta, uint32_t rest_sum_squares,
+                                           void *summary, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

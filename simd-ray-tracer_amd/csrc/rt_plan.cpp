@@ -179,6 +179,41 @@ int plan_tile_work(const rt_tile_work *work, uint32_t n_work, uint32_t width, ui
     return RT_OK;
 }
 
+int plan_tile_counts(bool have_device, bool lut_set, bool scene_set, const rt_camera_info *cam, const rt_trace_desc *desc,
+                     const uint32_t *tiles, uint32_t n_tiles, const void *d_counts, uint32_t max_frames,
+                     const void *d_delta, const uint64_t *d_rays, std::vector<uint32_t> &bits, TileCountsCall &out) {
+    if (!desc) return rt_fail(RT_EINVAL, "rt_trace: NULL argument");
+    if (!d_counts) return rt_fail(RT_EINVAL, "rt_trace_tile_counts: d_counts is NULL");
+    if (max_frames == 0u) return rt_fail(RT_EINVAL, "rt_trace_tile_counts: max_frames is 0");
+    if ((uintptr_t)d_delta & 15u) return rt_fail(RT_EINVAL, "rt_trace_tile_counts: d_delta is not 16-byte aligned");
+    out = TileCountsCall();
+    out.desc = *desc;  // (desc's own PreviousRayCount / Frames are not read: every tile has its entry)
+    out.desc.PreviousRayCount = 0;
+    out.desc.Frames = max_frames;
+    if (const int rc = check_trace_args(have_device, lut_set, scene_set, cam, &out.desc, d_rays)) return rc;
+    if (desc->BandCount > 1u || desc->BandIndex != 0u)
+        return rt_fail(RT_EINVAL, "rt_trace_tile_counts: tiles index the whole image (BandCount 0 or 1, BandIndex 0)");
+    if (!tiles && n_tiles) return rt_fail(RT_EINVAL, "rt_trace_tile_counts: tiles is NULL with n_tiles %u", n_tiles);
+    const ListName name = {"rt_trace_tile_counts", "tiles[", "]"};
+    if (const int rc = select_tiles(name, tiles, n_tiles, desc->Width, desc->Height, bits, out.sel)) return rc;
+    out.nothing = n_tiles == 0u;
+    return RT_OK;
+}
+
+int check_tile_step(const void *d_counts, const void *d_delta, uint32_t width, uint32_t height, const rt_tile_rule *rule,
+                    uint32_t *n_tiles) {
+    if (!d_counts || !d_delta || !rule) return rt_fail(RT_EINVAL, "rt_tile_counts_step: NULL argument");
+    if (rule->Size != sizeof(rt_tile_rule))
+        return rt_fail(RT_EINVAL, "rt_tile_rule: Size %u, this library's is %zu", rule->Size, sizeof(rt_tile_rule));
+    if (rule->MaxRoundFrames == 0u || rule->MaxTileFrames == 0u)
+        return rt_fail(RT_EINVAL, "rt_tile_rule: MaxRoundFrames %u, MaxTileFrames %u (both >= 1)", rule->MaxRoundFrames,
+                       rule->MaxTileFrames);
+    if ((uintptr_t)d_delta & 15u) return rt_fail(RT_EINVAL, "rt_tile_counts_step: d_delta is not 16-byte aligned");
+    *n_tiles = rt_tile_count(width, height, nullptr);
+    if (*n_tiles == 0u) return rt_fail(RT_EINVAL, "rt_tile_counts_step: bad image size %ux%u", width, height);
+    return RT_OK;
+}
+
 // The key: every word the cull masks, the live list and the learned order depend on.
 static void launch_key(const LaunchPlan &p, const SceneFacts &sf, int rs, const rt_trace_desc &desc,
                        const TileSelection *sel, const TraceArgs &a, std::vector<uint32_t> &key) {

@@ -145,6 +145,23 @@ struct TileWorkList {
 };
 int plan_tile_work(const rt_tile_work *work, uint32_t n_work, uint32_t width, uint32_t height, TileWorkList &out);
 
+// rt_trace_tile_counts without the device: everything the call refuses (rt_trace_tiles' refusals, a NULL
+// table, max_frames 0, a misaligned d_delta; the pointers are compared, never followed), its list as a
+// selection (the launch key's, as rt_trace_tiles builds it: nothing of the table enters it) and the
+// descriptor the launch is planned with -- desc with PreviousRayCount 0 and Frames = max_frames, the bound
+// that takes the place of the list's largest Frames in the launch shape.  `bits` is the caller's, reused.
+struct TileCountsCall {
+    TileSelection sel;
+    rt_trace_desc desc{};
+    bool nothing = false;  // n_tiles == 0: RT_OK, nothing to launch
+};
+int plan_tile_counts(bool have_device, bool lut_set, bool scene_set, const rt_camera_info *cam, const rt_trace_desc *desc,
+                     const uint32_t *tiles, uint32_t n_tiles, const void *d_counts, uint32_t max_frames,
+                     const void *d_delta, const uint64_t *d_rays, std::vector<uint32_t> &bits, TileCountsCall &out);
+// What rt_tile_counts_step refuses; *n_tiles = the image's reference tiles.
+int check_tile_step(const void *d_counts, const void *d_delta, uint32_t width, uint32_t height, const rt_tile_rule *rule,
+                    uint32_t *n_tiles);
+
 // Which table TraceArgs.clusters names.
 enum { kTableNone = 0, kTablePlain, kTableExpanded };
 // The rule set's two cluster tables on the device: opaque to the plan, which only chooses between them.

@@ -1,7 +1,7 @@
 // rt_sched.hip — the kernels around the trace launch: the primary-ray cull
 // pass, dead-tile fold, primary group rows, pixel sort, heaviest-first tile
-// sort, XCD grouping, RGBA8 encode, per-tile RGBA8 change statistics, ray-counter sum and band assembly, with
-// their launchers and the tile geometry queries.  A launch over a list of
+// sort, XCD grouping, RGBA8 encode, per-tile RGBA8 change statistics, the per-tile counts' table pass and stopping
+// rule, ray-counter sum and band assembly, with their launchers and the tile geometry queries.  A launch over a list of
 // reference tiles (rt_trace_tiles, TraceArgs.sel) is decided here alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -287,13 +287,17 @@ __global__ __launch_bounds__(256) void empty_counts_kernel(TraceArgs a, const ui
     constexpr uint32_t BW = 2u * Shape<P>::TW, BH = 2u * Shape<P>::TH;
     const uint32_t x = blockIdx.x * 256u + threadIdx.x, ly = blockIdx.y;
     // (dead tiles only: a tile outside the launch's selection is kTileSkipped and keeps every byte)
-    const bool dead = x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == kTileDead;
+    bool dead = x < a.width && live[(ly / BH) * a.tiles_x + x / BW] == kTileDead;
     uint32_t prev_count = 0, frames = 0;
     if (dead) {  // (a dead tile is a selected one: its reference tile has a pair)
         const uint32_t rt = (ly / kRefTile) * a.sel_tiles_x + x / kRefTile;
         const uint32_t *pair = rtk_tile_counts(a) + 2u * rt;
         prev_count = pair[0];
         frames = pair[1];
+        // a resting tile (rt_trace_tile_counts: a listed tile folding no frame) keeps every byte and
+        // counts no segment, like a tile outside the selection: with prev_count 0 the store below
+        // would otherwise write a zero mean
+        dead = frames != 0u;
     }
     unsigned long long seg = 0;
     if (dead && x % BW == 0u && ly % BH == 0u)
@@ -935,6 +939,108 @@ __global__ __launch_bounds__(256) void tile_delta_kernel(const float4 *accum, co
     }
 }
 }  // namespace rtk
+
+namespace rtk {
+// The table pass of rt_trace_tile_counts: the launch's internal counts table (rtk_sel_table_at) from the
+// caller's device table and the key's bitmap, one thread per reference tile of the image.  A listed tile
+// gets {prev, effective frames} (rtk_effective_frames), every other tile {0, 0} without its entry being
+// read: the trace and empty-tile kernels' pairs hold what the host-built table would (a pair that fits the
+// u32 frame count, frames <= the launch's), whatever the caller's memory holds.  `active` receives the
+// bitmap of the listed tiles that fold a frame, for the closing pass (a resting tile stores no RGBA8 and
+// no statistics): lane 0 of each wave stores its 64 tiles' two words with one 8-byte store (the bitmaps
+// are whole 64-tile words, 8-byte aligned: rtk_sel_table_at).
+__global__ __launch_bounds__(256) void counts_table_kernel(const uint32_t *counts, const uint32_t *sel, uint32_t n_tiles,
+                                                           uint32_t max_frames, uint2 *table, uint2 *active) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    uint2 pair = make_uint2(0u, 0u);
+    if (t < n_tiles) {
+        if ((sel[t >> 5] >> (t & 31u)) & 1u) {  // (the caller's struct is 4-byte aligned: two dword loads)
+            const uint32_t prev = counts[2u * t], f = rtk_effective_frames(prev, counts[2u * t + 1u], max_frames);
+            pair = make_uint2(f ? prev : 0u, f);
+        }
+        table[t] = pair;
+    }
+    const uint64_t m = __ballot(pair.y != 0u);
+    if ((threadIdx.x & 63u) == 0u && (t & ~63u) < n_tiles) active[t >> 6] = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+}
+
+// The library's per-tile stopping rule (rt_tile_counts_step; rt_trace.h states it): every entry of the
+// table that folded a frame in the round just traced advances by it and rests, or takes the next round's
+// frames by the doubling rule.  Integers only.  One block walks the image's tiles (8160 at 8K: eight per
+// thread), so the summary is a plain sum folded through the lanes and 1 KB of LDS -- no atomics, nothing
+// pre-zeroed, one value for a given input.
+constexpr uint32_t kStepBlock = 1024;
+__global__ __launch_bounds__(kStepBlock) void tile_counts_step_kernel(uint32_t *counts, const uint4 *delta, uint32_t n_tiles,
+                                                                      uint32_t max_round, uint32_t max_tile,
+                                                                      uint32_t rest_max_delta, uint32_t rest_sum_squares,
+                                                                      uint32_t *summary) {
+    __shared__ unsigned long long s_next[kStepBlock / 64u];
+    __shared__ uint32_t s_active[kStepBlock / 64u], s_rested[kStepBlock / 64u];
+    unsigned long long next = 0;
+    uint32_t active = 0, rested = 0;
+    for (uint32_t t = threadIdx.x; t < n_tiles; t += kStepBlock) {
+        const uint32_t prev = counts[2u * t];
+        const uint32_t f = rtk_effective_frames(prev, counts[2u * t + 1u], max_round);
+        if (f == 0u) continue;  // (a resting or impossible entry stays as it is and folds nothing next round either)
+        const uint32_t done = prev + f;  // (fits: rtk_effective_frames)
+        bool rest = done >= max_tile;
+        if (!rest && prev != 0u) {  // (a first round never rests on its statistics: "old" was the caller's)
+            const uint4 d = delta[t];
+            rest = d.y <= rest_max_delta && d.w <= rest_sum_squares;
+        }
+        // the doubling rule: as many frames again as the tile has, within the round's and the tile's bounds
+        // (done + these <= max_tile, so the new entry's effective frames are its Frames)
+        const uint32_t frames = rest ? 0u : min(done, min(max_round, max_tile - done));
+        counts[2u * t] = done;
+        counts[2u * t + 1u] = frames;
+        next += frames;
+        active += frames != 0u ? 1u : 0u;
+        rested += rest ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) {  // (every lane active)
+        next += __shfl_xor(next, off);
+        active += (uint32_t)__shfl_xor((int)active, off);
+        rested += (uint32_t)__shfl_xor((int)rested, off);
+    }
+    if (!summary) return;  // (launch-uniform)
+    const uint32_t w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+        s_next[w] = next;
+        s_active[w] = active;
+        s_rested[w] = rested;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (uint32_t i = 1; i < kStepBlock / 64u; ++i) {
+            next += s_next[i];
+            active += s_active[i];
+            rested += s_rested[i];
+        }
+        summary[0] = (uint32_t)next;  // (rt_tile_step_summary: u64 NextFrames, little-endian)
+        summary[1] = (uint32_t)(next >> 32);
+        summary[2] = active;
+        summary[3] = rested;
+    }
+}
+}  // namespace rtk
+
+extern "C" int rtk_launch_counts_table(const void *counts, const uint32_t *sel, uint32_t n_ref_tiles, uint32_t max_frames,
+                                       uint32_t *table, uint32_t *active, hipStream_t stream) {
+    if (!counts || !sel || !table || !active || n_ref_tiles == 0 || max_frames == 0) return -1;
+    hipLaunchKernelGGL(rtk::counts_table_kernel, dim3((n_ref_tiles + 255u) / 256u), dim3(256), 0, stream,
+                       (const uint32_t *)counts, sel, n_ref_tiles, max_frames, (uint2 *)table, (uint2 *)active);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int rtk_launch_tile_counts_step(void *counts, const void *delta, uint32_t n_ref_tiles, uint32_t max_round,
+                                           uint32_t max_tile, uint32_t rest_max_delta, uint32_t rest_sum_squares,
+                                           void *summary, hipStream_t stream) {
+    if (!counts || !delta || n_ref_tiles == 0 || max_round == 0 || max_tile == 0) return -1;
+    hipLaunchKernelGGL(rtk::tile_counts_step_kernel, dim3(1), dim3(rtk::kStepBlock), 0, stream, (uint32_t *)counts,
+                       (const uint4 *)delta, n_ref_tiles, max_round, max_tile, rest_max_delta, rest_sum_squares,
+                       (uint32_t *)summary);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
 
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0u; }
 

@@ -245,7 +245,22 @@ void trace_kernel(TraceArgs a) {
         const uint32_t *pair = a.sel + a.tile_counts_at + 2u * rt;  // (rtk_tile_counts: the host launches these kernels with a table)
         a.prev_count = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair[0]);
         a.frames = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair[1]);
-        // (the host lists no tile with Frames == 0: the launch fact of the walk kernels holds per tile)
+        // A resting tile (rt_trace_tile_counts: a listed tile whose device entry folds no frame) leaves
+        // here, before any barrier, LDS fill or store: the block tile is workgroup-uniform, so every wave
+        // of the workgroup takes the branch.  A launch that measures costs still needs one from this
+        // unit -- the sort zeroed it, and cost 0 ranks with the dead tiles behind the live prefix the
+        // next grid covers -- so it gets the smallest a launched unit can have (the end of the kernel).
+        // Its pixels' costs (pix_cost) stay those of the tile's last traced launch.
+        if (a.frames == 0u) {
+            if (a.tile_cost && (threadIdx.x & 63u) == 0u) {
+                if (SOLO && a.unit_waves != 0u)
+                    a.tile_cost[4u * t0 + w0] = 1u;
+                else
+                    atomicMax(a.tile_cost + t0, 1u);
+            }
+            return;
+        }
+        // (so every tile that stays has Frames >= 1: the launch fact of the walk kernels holds per tile)
         if constexpr (SOLO && WALK != kWalkAny) __builtin_assume(a.frames != 0u);
     }
     TraceStats<kStats> st(a.stats);  // (the -DRTK_STATS build's counters; empty otherwise)
