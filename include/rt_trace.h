@@ -489,6 +489,65 @@ typedef struct rt_tile_step_summary {
 int rt_tile_counts_step(rt_tile_counts *d_counts, const rt_tile_delta *d_delta, uint32_t width, uint32_t height,
                         const rt_tile_rule *rule, rt_tile_step_summary *d_summary, void *stream);
 
+/* ------------------------------------------------- what a pixel sees: the first hit */
+
+#define RT_HIT_MISS   0xFFFFFFFFu   /* rt_first_hit.Key of a pixel whose primary ray hits nothing      */
+#define RT_HIT_INSIDE 0x80000000u   /* bit 31 of Key: the reference's InsideSphere flag of the winner  */
+#define RT_HIT_PIXEL_CENTRE 1u      /* flags: Jx = Jy = 0, no RNG draw                                  */
+
+typedef struct rt_first_hit {       /* 8 B per pixel */
+    uint32_t Key;                   /* MaterialIndex (4*group + lane == index into ScalarSpheres), | RT_HIT_INSIDE; or RT_HIT_MISS */
+    float    T;                     /* MinT of the first segment (main.cpp:413-429); 1e30f (F32Max) on a miss */
+} rt_first_hit;
+
+typedef struct rt_first_hit_planes {
+    uint32_t      Size;             /* sizeof(rt_first_hit_planes) */
+    rt_first_hit *Hit;              /* DEVICE, Width*Height entries, 8-byte aligned, or NULL  */
+    float        *Normal;           /* DEVICE, Width*Height v4 f32, 16-byte aligned, or NULL  */
+    float        *Albedo;           /* DEVICE, Width*Height v4 f32, 16-byte aligned, or NULL  */
+} rt_first_hit_planes;
+
+/* The first segment of every pixel's path as a pass of its own: which sphere the primary ray hits, how
+ * far away, with which normal and which surface colour -- for picking, for a denoiser's or a stopping
+ * rule's guide images, and for naming the sphere behind a pixel in question.  New; the reference keeps
+ * these values inside RenderTile's first loop iteration (main.cpp:375-444).
+ *  - The ray is the primary ray of frame k = desc->PreviousRayCount of rt_trace with the same cam, Width
+ *    and Height: the seed rt_pixel_seed(x, y, k, Width, Height), two RandomFloat draws, the film point
+ *    and Normalize of main.cpp:375-385 -- the trace kernel's own function.  With RT_HIT_PIXEL_CENTRE in
+ *    `flags` both jitters are exactly 0.0f and no RNG is touched; every later operation is the same
+ *    sequence.  desc->Frames, MaxBounce, Flags and the image fields of cam are not read.
+ *  - The hit is the reference's first loop iteration under the rule set desc->EnableSIMD selects, sphere
+ *    loop and hit select: the SIMD rules' per-class minima, first-equal-lane select and sticky inside
+ *    flag (main.cpp:399-444), or the scalar rules' "later sphere wins a tie" and non-sticky flag
+ *    (main.cpp:541-578).  The same device functions as the trace kernel's first segment, so the same bits.
+ *  - Hit[y * Width + x] = {MaterialIndex | inside << 31, MinT} of the winner.  Normal = Normalize(D * MinT
+ *    - C), negated when the inside flag is set, as the shading step forms HitNormal (main.cpp:423-429,
+ *    452-457), with w = 0 -- the reference's Normalize, so the zero vector where the squared length, the winner's
+ *    r^2, is <= 1e-4 (x64_math.h:234-245).  Albedo = the winner's Material.Color.xyz with w = 1.  A miss writes
+ *    {RT_HIT_MISS, 1e30f} and zeros to the other two planes (Albedo.w = 0 marks it).
+ *  - tiles == NULL with n_tiles == 0 selects every tile of the image.  Otherwise tiles is a HOST list of
+ *    reference tiles validated exactly as rt_trace_tiles validates its list (the same refusals, the same
+ *    clipping), consumed before the call returns.  Only the pixels of listed tiles are written, in each
+ *    non-NULL plane: no byte of any other pixel, and nothing at all in a NULL plane.  A non-NULL list with
+ *    n_tiles == 0 returns RT_OK with nothing enqueued.
+ *  - RT_EINVAL, before anything is enqueued or changed: a NULL dev, cam, desc or out; a wrong Size; all
+ *    three planes NULL; a misaligned plane; a flag bit other than RT_HIT_PIXEL_CENTRE; SeedMode other than
+ *    RT_SEED_PIXEL; BandCount not 0 or 1, or BandIndex != 0; an image for which rt_tile_count is 0; no
+ *    uploaded scene; tiles == NULL with n_tiles > 0, a tile index out of range or named twice.  The rsqrt
+ *    table is not required: the pass never calls NormalizeFast.
+ *  - No effect on tracing: the pass takes no d_rays and counts nothing; it neither reads nor creates nor
+ *    replaces the device's launch key, cull masks, tile order, costs or pixel permutation (it culls inside
+ *    its kernel, per 8x8 pixel tile, and keeps nothing); rt_trace_last_info and rt_trace_last_tile_counts
+ *    report after the call what they reported before it, and the next rt_trace of an unchanged key has
+ *    CullPassRan == 0.
+ *  - Asynchronous on `stream` under the stream rule of rt_trace (one stream per device; a switch waits for
+ *    the device); rt_scene_upload waits for this pass as it waits for trace launches.  A tile list is
+ *    uploaded through a bitmap and pinned staging of the pass's own; rt_device_reserve covers them for its
+ *    width x local_rows, and the call waits only where rt_trace_tiles may wait. */
+int rt_trace_first_hit(rt_device *dev, const rt_camera_info *cam, const rt_trace_desc *desc,
+                       const uint32_t *tiles, uint32_t n_tiles, uint32_t flags,
+                       const rt_first_hit_planes *out, void *stream);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call
@@ -562,7 +621,8 @@ int rt_trace_last_tile_counts(rt_device *dev, uint32_t *out);
  * the upload still succeeds and the reservation is dropped: later launches
  * grow their buffers as they need).  Also sizes what rt_trace_tiles needs for
  * a width x local_rows image (the selection bitmap and its pinned staging) and
- * what rt_trace_tile_work needs beyond that (the per-tile table and its staging).
+ * what rt_trace_tile_work needs beyond that (the per-tile table and its staging),
+ * and rt_trace_first_hit's own bitmap and staging.
  * Waits for the device.  (New; the reference's arena is sized once in OnInit,
  * main.cpp:658.) */
 int rt_device_reserve(rt_device *dev, uint32_t width, uint32_t local_rows);

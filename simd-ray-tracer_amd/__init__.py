@@ -124,6 +124,19 @@ tile_counts_dtype = np.dtype([(n, "<u4") for n, _ in RtTileCounts._fields_])
 tile_step_summary_dtype = np.dtype([("NextFrames", "<u8"), ("ActiveTiles", "<u4"), ("RestedNow", "<u4")])
 
 
+class RtFirstHit(ctypes.Structure):  # rt_first_hit: one pixel of rt_trace_first_hit's Hit plane, 8 B
+    _fields_ = [("Key", c_uint32), ("T", c_float)]
+
+
+class RtFirstHitPlanes(ctypes.Structure):  # rt_first_hit_planes: the device planes rt_trace_first_hit writes, 32 B
+    _fields_ = [("Size", c_uint32), ("Hit", c_void_p), ("Normal", c_void_p), ("Albedo", c_void_p)]
+
+
+# a copied-back Hit plane: np.frombuffer(bytes, first_hit_dtype).reshape(height, width)
+first_hit_dtype = np.dtype([("Key", "<u4"), ("T", "<f4")])
+HIT_MISS, HIT_INSIDE, HIT_PIXEL_CENTRE = 0xFFFFFFFF, 0x80000000, 1
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -209,6 +222,8 @@ SIGNATURES = {
     "rt_trace_tile_counts": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32,
                                      c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "rt_tile_counts_step": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(RtTileRule), c_void_p, c_void_p]),
+    "rt_trace_first_hit": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32, c_uint32,
+                                   POINTER(RtFirstHitPlanes), c_void_p]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -616,6 +631,31 @@ class Device:
                                           c_void_p(t.ctypes.data if t.size else None), int(t.size),
                                           c_void_p(counts_ptr or None), int(max_frames), c_void_p(delta_ptr or None),
                                           c_void_p(rays_ptr), c_void_p(stream or 0)), "rt_trace_tile_counts")
+
+    def trace_first_hit(self, cam: RtCameraInfo, *, width: int, height: int, frame: int = 0, simd: bool = True,
+                        centre: bool = False, tiles=None, hit_ptr: int = 0, normal_ptr: int = 0, albedo_ptr: int = 0,
+                        stream: Optional[int] = 0) -> None:
+        """What every pixel sees (rt_trace_first_hit): the first segment of frame `frame`'s primary ray --
+        the ray trace() starts at prev_count == frame, or with `centre` the ray through the pixel centre --
+        under the rule set `simd`.  `hit_ptr` (width * height first_hit_dtype entries: the sphere index,
+        HIT_INSIDE in bit 31, or HIT_MISS; the distance), `normal_ptr` and `albedo_ptr` (width * height v4
+        f32 each) are device pointers, each optional but not all.  `tiles` (None: every tile) lists the
+        32 x 32 tiles to write, as trace_tiles; no other pixel is written.  Asynchronous on `stream`;
+        nothing of the device's trace state changes."""
+        t = None
+        if tiles is not None:
+            t = np.ascontiguousarray(np.asarray(list(tiles) if not isinstance(tiles, np.ndarray) else tiles).reshape(-1))
+            if t.size and (t.dtype.kind not in "iu" or int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+                raise ValueError("tiles: a sequence of tile indices (non-negative integers)")
+            t = t.astype(np.uint32)
+        d = RtTraceDesc(width, height, frame, 0, 0, 1 if simd else 0, RT_SEED_PIXEL, 0, 1, 0, 0)
+        planes = RtFirstHitPlanes(ctypes.sizeof(RtFirstHitPlanes), hit_ptr or None, normal_ptr or None, albedo_ptr or None)
+        # (an empty list stays a list: a non-NULL pointer with n_tiles == 0 is "nothing to do", not "every tile")
+        empty = np.zeros(1, np.uint32)
+        ptr = None if t is None else (t.ctypes.data if t.size else empty.ctypes.data)
+        _check(lib().rt_trace_first_hit(self.handle, ctypes.byref(cam), ctypes.byref(d), c_void_p(ptr),
+                                        0 if t is None else int(t.size), HIT_PIXEL_CENTRE if centre else 0,
+                                        ctypes.byref(planes), c_void_p(stream or 0)), "rt_trace_first_hit")
 
     def last_info(self) -> dict:
         """What the last trace launched (rt_trace_last_info): segments counted

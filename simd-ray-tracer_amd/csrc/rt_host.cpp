@@ -81,6 +81,16 @@ struct SelectionStaging {
     TileWorkList work;               // rt_trace_tile_work's list, bitmap and table (no allocation per call)
 };
 
+// rt_trace_first_hit: the bitmap of the call's tile list on the device and the two pinned slots it is
+// uploaded from (StagedWords).  The pass's own: the key's selection buffer above, which a later
+// rt_trace_tiles of the same list expects to find as it left it, is never touched.
+struct FirstHitStaging {
+    uint32_t *d_sel = nullptr;
+    StagedWords bits;
+    size_t cap = 0;                   // reference tiles d_sel and the pinned slots are sized for
+    std::vector<uint32_t> tile_bits;  // the call's bitmap is built here (no allocation per call)
+};
+
 // The cull pass's totals travel to the host asynchronously (pinned h_counts,
 // event ev_counts): a new key never blocks the host.  Until they have
 // landed (known), launches size their grids for every tile and read
@@ -126,6 +136,7 @@ struct rt_device {
     bool scene_set = false;
     TileState tiles;
     SelectionStaging sel;
+    FirstHitStaging first_hit;
     AsyncTotals totals;
     LastLaunch last;
 };
@@ -240,9 +251,10 @@ extern "C" int rt_device_destroy(rt_device *d) {
             (void)hipFree(p);
     for (void *p : {(void *)d->d_lut, (void *)d->d_weights, (void *)d->d_stats, (void *)d->d_wave_times, (void *)t.cost,
                     (void *)t.order, (void *)t.order_sorted, (void *)t.aux, (void *)t.scratch, (void *)t.live,
-                    (void *)t.cull_counters, (void *)t.masks, (void *)t.pix_perm, (void *)t.pix_cost, (void *)d->sel.d_sel})
+                    (void *)t.cull_counters, (void *)t.masks, (void *)t.pix_perm, (void *)t.pix_cost, (void *)d->sel.d_sel,
+                    (void *)d->first_hit.d_sel})
         (void)hipFree(p);
-    for (StagedWords *w : {&d->sel.bits, &d->sel.counts}) {
+    for (StagedWords *w : {&d->sel.bits, &d->sel.counts, &d->first_hit.bits}) {
         for (int i = 0; i < 2; ++i) {
             if (w->h[i]) (void)hipHostFree(w->h[i]);
             if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
@@ -502,6 +514,28 @@ static int ensure_sel(rt_device *d, uint32_t ref_tiles, hipStream_t sync, bool d
     return grown(d);
 }
 
+// rt_trace_first_hit's bitmap for images of up to `ref_tiles` reference tiles, and its two pinned slots
+// (ensure_sel's scheme).  Nothing of the launch key depends on it: no key is cleared, no growth counted.
+static int ensure_first_hit_sel(rt_device *d, uint32_t ref_tiles, hipStream_t sync, bool device_wide) {
+    FirstHitStaging &s = d->first_hit;
+    if (ref_tiles <= s.cap) return RT_OK;
+    if (const int rc = wait_for(sync, device_wide)) return rc;
+    release({want(s.d_sel, 0)});
+    s.cap = 0;
+    const size_t words = rtk_sel_table_at(ref_tiles);  // (the bitmap's words rounded up to a whole u64)
+    for (int i = 0; i < 2; ++i) {
+        StagedWords &w = s.bits;
+        if (w.h[i]) (void)hipHostFree(w.h[i]);
+        w.h[i] = nullptr;
+        w.in_flight[i] = false;
+        if (!w.ev[i] && hipEventCreateWithFlags(&w.ev[i], hipEventDisableTiming) != hipSuccess)
+            return fail(RT_ENOMEM, "rt_trace_first_hit: upload event");
+        if (hipHostMalloc(&w.h[i], words * 4u, hipHostMallocDefault) != hipSuccess)
+            return fail(RT_ENOMEM, "rt_trace_first_hit: pinned staging");
+    }
+    return regrow(s.cap, ref_tiles, {want(s.d_sel, words * 4u)}, "rt_trace_first_hit: selection buffer");
+}
+
 // n words -> dst (device) on `s`, through the pinned slot not used last.  The slot's previous copy
 // (two uploads ago) has normally finished long since; if not, the host waits for it here -- the
 // one place rt_trace_tiles and rt_trace_tile_work may block beyond rt_trace's own.
@@ -529,6 +563,7 @@ static int apply_reserve(rt_device *d) {
         for (const SceneFacts &f : d->facts) n_words = std::max(n_words, rtk_mask_words(f.n_groups));
     if (const int rc = ensure_tile_buffers(d, n_tiles, nullptr, true)) return rc;
     if (const int rc = ensure_sel(d, t.reserve_ref_tiles, nullptr, true)) return rc;  // (rt_trace_tiles, rt_trace_tile_work)
+    if (const int rc = ensure_first_hit_sel(d, t.reserve_ref_tiles, nullptr, true)) return rc;  // (rt_trace_first_hit)
     if (d->sw.pixel_sort)
         if (const int rc = ensure_pixel_sort(d, n_tiles, t.reserve_pixels, nullptr, true)) return rc;
     return ensure_masks(d, (size_t)n_tiles * 4u * n_words, nullptr, true);
@@ -986,6 +1021,45 @@ extern "C" int rt_tile_counts_step(rt_tile_counts *d_counts, const rt_tile_delta
     if (rtk_launch_tile_counts_step(d_counts, d_delta, n_tiles, rule->MaxRoundFrames, rule->MaxTileFrames,
                                     rule->RestMaxDelta, rule->RestSumSquares, d_summary, (hipStream_t)stream) != 0)
         return fail(RT_EIO, "rt_tile_counts_step: launch failed");
+    return RT_OK;
+}
+
+// The first segment of every pixel of the listed tiles as a pass of its own (rt_first_hit.hip).  Nothing of the
+// launch state is read or written: no key, masks, order, costs or totals, and d->last stays what it was.
+extern "C" int rt_trace_first_hit(rt_device *d, const rt_camera_info *cam, const rt_trace_desc *desc, const uint32_t *tiles,
+                                  uint32_t n_tiles, uint32_t flags, const rt_first_hit_planes *out, void *stream) {
+    DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (!d) return fail(RT_EINVAL, "rt_trace_first_hit: NULL argument");
+    // the device-free plan of the call (rt_plan.cpp): its refusals and the list's selection.  The list is
+    // consumed here (the bitmap lives in the device's own host vector), so the caller's array is free on return.
+    FirstHitCall call;
+    if (const int rc = plan_first_hit(true, d->scene_set, cam, desc, tiles, n_tiles, flags, out, d->first_hit.tile_bits, call))
+        return rc;
+    if (call.nothing) return RT_OK;
+    const int rs = desc->EnableSIMD ? 0 : 1;
+    TraceArgs a;
+    fill_args(d, cam, desc, rs, desc->Height, nullptr, a);
+    // (what the pass does not read stays out of its arguments: the images, Frames, MaxBounce and Flags)
+    a.prev = nullptr;
+    a.cur = nullptr;
+    a.frames = a.max_bounce = a.flags = 0u;
+    const SceneFacts &f = d->facts[rs];
+    a.n_groups = f.n_groups;
+    a.n_spheres = f.n_spheres;
+    a.fast_sqrt = f.fast_sqrt;  // the scene fact the trace launches use
+    a.tiles_x = rtk_tiles_x(desc->Width, 1);
+    HIP_OK(hipSetDevice(d->ordinal));
+    hipStream_t s = (hipStream_t)stream;  // NULL = the HIP null stream
+    if (const int rc = switch_stream(d, s)) return rc;
+    if (!call.all) {
+        if (const int rc = ensure_first_hit_sel(d, call.sel.n_tiles, s, false)) return rc;
+        if (const int rc = staged_upload(d->first_hit.bits, d->first_hit.d_sel, call.sel.bits, call.sel.n_words, s)) return rc;
+        a.sel = d->first_hit.d_sel;
+        a.sel_tiles_x = call.sel.tiles_x;
+    }
+    if (rtk_launch_first_hit(&a, desc->EnableSIMD ? 1 : 0, d->sw.cull, (flags & RT_HIT_PIXEL_CENTRE) ? 1 : 0, out->Hit,
+                             out->Normal, out->Albedo, s) != 0)
+        return fail(RT_EIO, "rt_trace_first_hit: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return RT_OK;
 }
 

@@ -1,5 +1,5 @@
 // rt_kernel.h — launch contract between the C-ABI host (rt_host.cpp, its launch decisions rt_plan.cpp) and the
-// gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_trace_tc.hip, rt_sched.hip).  Internal; not part of include/.
+// gfx950 kernels (rt_trace.hip, rt_trace_p16.hip, rt_trace_tc.hip, rt_sched.hip, rt_first_hit.hip).  Internal; not part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -305,6 +305,13 @@ extern "C" int rtk_launch_counts_table(const void *counts, const uint32_t *sel, 
 extern "C" int rtk_launch_tile_counts_step(void *counts, const void *delta, uint32_t n_ref_tiles, uint32_t max_round,
                                            uint32_t max_tile, uint32_t rest_max_delta, uint32_t rest_sum_squares,
                                            void *summary, hipStream_t stream);
+// rt_trace_first_hit (rt_first_hit.hip): the first segment of frame a->prev_count of every pixel of the selected
+// reference tiles (a->sel, or every tile), under the rule set `simd`, culled in the kernel (`cull`) or tested
+// against every pair; centre: RT_HIT_PIXEL_CENTRE.  Reads of *a: the camera and the image size, groups,
+// materials, n_groups, n_spheres, fast_sqrt, sel, sel_tiles_x and tiles_x (= rtk_tiles_x(width, 1)).  The planes
+// (DEVICE; rt_first_hit, v4 f32, v4 f32; each may be NULL, not all) are arguments of their own: TraceArgs does not grow.
+extern "C" int rtk_launch_first_hit(const TraceArgs *a, int simd, int cull, int centre, void *hit, float *normal,
+                                    float *albedo, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

@@ -214,6 +214,34 @@ int check_tile_step(const void *d_counts, const void *d_delta, uint32_t width, u
     return RT_OK;
 }
 
+int plan_first_hit(bool have_device, bool scene_set, const rt_camera_info *cam, const rt_trace_desc *desc,
+                   const uint32_t *tiles, uint32_t n_tiles, uint32_t flags, const rt_first_hit_planes *out,
+                   std::vector<uint32_t> &bits, FirstHitCall &call) {
+    if (!have_device || !cam || !desc || !out) return rt_fail(RT_EINVAL, "rt_trace_first_hit: NULL argument");
+    if (out->Size != sizeof(rt_first_hit_planes))
+        return rt_fail(RT_EINVAL, "rt_first_hit_planes: Size %u, this library's is %zu", out->Size, sizeof(rt_first_hit_planes));
+    if (!out->Hit && !out->Normal && !out->Albedo) return rt_fail(RT_EINVAL, "rt_trace_first_hit: every plane is NULL");
+    if ((uintptr_t)out->Hit & 7u) return rt_fail(RT_EINVAL, "rt_trace_first_hit: Hit is not 8-byte aligned");
+    if ((uintptr_t)out->Normal & 15u) return rt_fail(RT_EINVAL, "rt_trace_first_hit: Normal is not 16-byte aligned");
+    if ((uintptr_t)out->Albedo & 15u) return rt_fail(RT_EINVAL, "rt_trace_first_hit: Albedo is not 16-byte aligned");
+    if (flags & ~RT_HIT_PIXEL_CENTRE) return rt_fail(RT_EINVAL, "rt_trace_first_hit: unknown flags 0x%x", flags);
+    if (desc->SeedMode != RT_SEED_PIXEL) return rt_fail(RT_EINVAL, "rt_trace_first_hit: only RT_SEED_PIXEL runs on the GPU");
+    if (desc->BandCount > 1u || desc->BandIndex != 0u)
+        return rt_fail(RT_EINVAL, "rt_trace_first_hit: the planes are whole images (BandCount 0 or 1, BandIndex 0)");
+    if (rt_tile_count(desc->Width, desc->Height, nullptr) == 0u)
+        return rt_fail(RT_EINVAL, "rt_trace_first_hit: bad image size %ux%u", desc->Width, desc->Height);
+    if (!scene_set) return rt_fail(RT_EINVAL, "rt_trace_first_hit: no scene uploaded (rt_scene_upload)");
+    if (!tiles && n_tiles) return rt_fail(RT_EINVAL, "rt_trace_first_hit: tiles is NULL with n_tiles %u", n_tiles);
+    call = FirstHitCall();
+    const ListName name = {"rt_trace_first_hit", "tiles[", "]"};
+    // (a refused list has been written into `bits` up to the index refused: scratch of this pass alone, rebuilt by
+    // every call before anything reads it, so nothing a later call or the launch key sees has changed)
+    if (const int rc = select_tiles(name, tiles, n_tiles, desc->Width, desc->Height, bits, call.sel)) return rc;
+    call.all = tiles == nullptr;
+    call.nothing = !call.all && n_tiles == 0u;
+    return RT_OK;
+}
+
 // The key: every word the cull masks, the live list and the learned order depend on.
 static void launch_key(const LaunchPlan &p, const SceneFacts &sf, int rs, const rt_trace_desc &desc,
                        const TileSelection *sel, const TraceArgs &a, std::vector<uint32_t> &key) {

@@ -162,6 +162,18 @@ int plan_tile_counts(bool have_device, bool lut_set, bool scene_set, const rt_ca
 int check_tile_step(const void *d_counts, const void *d_delta, uint32_t width, uint32_t height, const rt_tile_rule *rule,
                     uint32_t *n_tiles);
 
+// rt_trace_first_hit without the device: everything the call refuses (the planes' pointers are compared,
+// never followed) and its list as a selection, built by select_tiles as rt_trace_tiles builds its own.
+// `bits` is the caller's, reused; it belongs to this pass (the launch key's bitmap is another vector).
+struct FirstHitCall {
+    TileSelection sel;     // (all: no bitmap, only the image's tile counts)
+    bool all = false;      // tiles == NULL with n_tiles == 0: every tile of the image
+    bool nothing = false;  // a list with n_tiles == 0: RT_OK, nothing to launch
+};
+int plan_first_hit(bool have_device, bool scene_set, const rt_camera_info *cam, const rt_trace_desc *desc,
+                   const uint32_t *tiles, uint32_t n_tiles, uint32_t flags, const rt_first_hit_planes *out,
+                   std::vector<uint32_t> &bits, FirstHitCall &call);
+
 // Which table TraceArgs.clusters names.
 enum { kTableNone = 0, kTablePlain, kTableExpanded };
 // The rule set's two cluster tables on the device: opaque to the plan, which only chooses between them.

@@ -225,11 +225,13 @@ __device__ __forceinline__ uint32_t at_use(uint32_t v) {
     return v;
 }
 
-template <typename Args>
+// CENTRE (the first-hit pass's RT_HIT_PIXEL_CENTRE): both jitters are exactly 0 and no RNG is touched
+// (p.rng is left 0); every operation from the film point on is the same sequence.
+template <bool CENTRE = false, typename Args>
 __device__ __forceinline__ void start_sample(const Args &a, uint32_t x, uint32_t y, uint32_t frame, Sample &p) {
-    p.rng = seed_mix(((uint64_t)frame * a.height + y) * a.width + x);
-    const float jx = rand_float(p.rng, -0.5f, kInvRange1);
-    const float jy = rand_float(p.rng, -0.5f, kInvRange1);
+    p.rng = CENTRE ? 0ull : seed_mix(((uint64_t)frame * a.height + y) * a.width + x);
+    const float jx = CENTRE ? 0.0f : rand_float(p.rng, -0.5f, kInvRange1);
+    const float jy = CENTRE ? 0.0f : rand_float(p.rng, -0.5f, kInvRange1);
     // ((x + Jx) * 2) / W with (f32)W and its reciprocal RN(1/W) from the host: the
     // numerator is +0 or >= 2^-24 (Jx = -0.5 + r is never -0), so div_rn's
     // range condition holds
