@@ -196,6 +196,8 @@ typedef struct rt_device_options {
     int32_t SplitGrowth;         /* each leading part this many times the previous (0: 3)            */
     int32_t OrderLaunches;       /* re-sorts per key before the order is kept (0: 4; -1: none)       */
     int32_t EncodePass;          /* RGBA8 by a coalesced pass after multi-frame launches (default on) */
+    int32_t DirectionTable;      /* member entries chosen by the direction table (default: launches  */
+                                 /* of at most 8 lanes per pixel; ON: 16 too; OFF: no table built)   */
 } rt_device_options;
 
 /* rt_device_create with options (NULL: the defaults).  RT_EINVAL for a value
@@ -609,6 +611,10 @@ int rt_trace_last_info(rt_device *dev, rt_trace_info *out);
  * launch rt_trace_last_info's SegmentsFolded is summed on the device -- each dead block tile's in-image
  * pixels times its own tile's frames -- and that call waits for the sum as it does for the cull totals. */
 int rt_trace_last_tile_counts(rt_device *dev, uint32_t *out);
+/* *out = 1 when the last launch's kernel chose its member entries by the direction table
+ * (rt_scene_direction_table; rt_trace_info.Walk is then 2 as for the cluster walk it replaces), else 0.
+ * A query of its own, as rt_trace_last_tile_counts is.  Host-side bookkeeping, never waits. */
+int rt_trace_last_direction_table(rt_device *dev, uint32_t *out);
 
 /* Pre-sizes the device's launch buffers (tile order / cost / live lists, the
  * cull pass's masks and counters) for bands of up to `width` x `local_rows`
@@ -851,6 +857,31 @@ int rt_scene_clusters_expanded(const rt_scene *scene, uint32_t enable_simd, floa
  * index the member entries) or 0 (no table). */
 int rt_scene_cluster_layout(const rt_scene *scene, uint32_t enable_simd, uint32_t *out_levels,
                             uint32_t *out_sub_pairs);
+/* The direction table of a one-word scene-wide table whose expanded form is in use (test/inspection hook;
+ * DESIGN.md §3, "the direction table"): Rows rows, one per sphere slot, of CellsPerRow masks of MaskBits
+ * bits (32 up to 32 sphere pairs, else 64), row-major.  Bit p of row j, cell c is set when a ray with
+ * |D|^2 within 2^-16 of 1 and rt_direction_cell(D) == c whose origin lies within 1.008 r_j of sphere j's
+ * centre can be accepted by the exact test on sphere 2p or 2p + 1; the bit of j's own pair is always
+ * set, and a cell no such direction reaches is all-ones.  A secondary round of the walk-specialised
+ * one-wave kernels then tests only the member entries of the union of its lanes' masks.  *out_bytes = the
+ * table's size (0: the scene has none; info is then all 0); out may be NULL to query the size. */
+typedef struct rt_direction_table_info {
+    uint32_t CellsPerEdge; /* n: a face of the direction grid is n x n cells        */
+    uint32_t MaskBits;     /* 32 or 64                                              */
+    uint32_t Rows;         /* sphere slots: 4 x groups                              */
+    uint32_t CellsPerRow;  /* 6 n^2                                                 */
+} rt_direction_table_info;
+int rt_scene_direction_table(const rt_scene *scene, uint32_t enable_simd, void *out, uint64_t capacity_bytes,
+                             uint64_t *out_bytes, rt_direction_table_info *info);
+/* The member entries that walk reads: entry p = the sphere pair {2p, 2p + 1} in the layout and with the
+ * values of the rt_scene_clusters_expanded member entries (4 float4 rows each; a sphere outside the
+ * table: threshold -inf, no bit).  *out_f4 = float4 rows (0: none). */
+int rt_scene_direction_members(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
+                               uint32_t *out_f4);
+/* The cell of direction D, bit for bit the kernel's own function (IEEE compares, one FMA, floor and clamp
+ * per axis): face = the largest component by magnitude and its sign, the other two components index the
+ * face's n x n grid as they are. */
+uint32_t rt_direction_cell(float dx, float dy, float dz);
 const char *rt_last_error(void);
 
 /* ----------------------------------------------- OnInit / OnRender driver */

@@ -141,7 +141,7 @@ OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterC
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
                  "PixelSort", "PixelSegment", "XcdGroup", "SplitFirstLaunch", "HeadSamples", "SplitParts",
-                 "SplitGrowth", "OrderLaunches", "EncodePass")
+                 "SplitGrowth", "OrderLaunches", "EncodePass", "DirectionTable")
 RT_OPT_DEFAULT, RT_OPT_ON, RT_OPT_OFF = 0, 1, -1
 
 
@@ -173,6 +173,10 @@ def parse_options(items) -> dict:
         if out[k.strip()] is None:
             out[k.strip()] = int(v)
     return out
+
+
+class RtDirectionTableInfo(ctypes.Structure):  # rt_direction_table_info
+    _fields_ = [(n, c_uint32) for n in ("CellsPerEdge", "MaskBits", "Rows", "CellsPerRow")]
 
 
 class RtMultiInfo(ctypes.Structure):  # rt_multi_get_info
@@ -261,6 +265,11 @@ SIGNATURES = {
     "rt_scene_clusters_expanded": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32),
                                            POINTER(ctypes.c_float), POINTER(c_uint32)]),
     "rt_scene_cluster_layout": (c_int, [POINTER(RtScene), c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
+    "rt_scene_direction_table": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint64, POINTER(c_uint64),
+                                         POINTER(RtDirectionTableInfo)]),
+    "rt_scene_direction_members": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32)]),
+    "rt_direction_cell": (c_uint32, [c_float, c_float, c_float]),
+    "rt_trace_last_direction_table": (c_int, [c_void_p, POINTER(c_uint32)]),
     "rt_last_error": (c_char_p, []),
     "rt_on_init": (c_int, [POINTER(RtInitParams)]),
     "rt_on_init_devices": (c_int, [POINTER(RtInitParams), POINTER(c_int), c_uint32]),
@@ -506,6 +515,38 @@ def scene_cluster_layout(scene: RtScene, simd: bool = True):
     return int(lv.value), int(sp.value)
 
 
+def scene_direction_table(scene: RtScene, simd: bool = True):
+    """The direction table of a one-word scene-wide table (rt_scene_direction_table): (masks shaped
+    (Rows, CellsPerRow), uint32 or uint64 -- None where the scene has no table --, cells per face edge)."""
+    nbytes, info = c_uint64(), RtDirectionTableInfo()
+    _check(lib().rt_scene_direction_table(ctypes.byref(scene), int(simd), None, 0, ctypes.byref(nbytes),
+                                          ctypes.byref(info)), "rt_scene_direction_table")
+    if not nbytes.value:
+        return None, 0
+    tab = np.zeros((info.Rows, info.CellsPerRow), np.uint64 if info.MaskBits == 64 else np.uint32)
+    assert tab.nbytes == nbytes.value
+    _check(lib().rt_scene_direction_table(ctypes.byref(scene), int(simd), tab.ctypes.data, tab.nbytes,
+                                          ctypes.byref(nbytes), ctypes.byref(info)), "rt_scene_direction_table")
+    return tab, int(info.CellsPerEdge)
+
+
+def scene_direction_members(scene: RtScene, simd: bool = True) -> np.ndarray:
+    """The direction walk's member entries in pair order (rt_scene_direction_members): (pairs, 4, 4) f32."""
+    nf4 = c_uint32()
+    _check(lib().rt_scene_direction_members(ctypes.byref(scene), int(simd), None, 0, ctypes.byref(nf4)),
+           "rt_scene_direction_members")
+    tab = np.zeros((nf4.value, 4), np.float32)
+    if nf4.value:
+        _check(lib().rt_scene_direction_members(ctypes.byref(scene), int(simd), tab.ctypes.data, nf4.value,
+                                                ctypes.byref(nf4)), "rt_scene_direction_members")
+    return tab.reshape(-1, 4, 4)
+
+
+def direction_cell(dx, dy, dz) -> int:
+    """rt_direction_cell: the kernel's own cell function."""
+    return int(lib().rt_direction_cell(float(dx), float(dy), float(dz)))
+
+
 def rsqrt_table_builtin() -> np.ndarray:
     t = np.zeros(2048, np.float32)
     _check(lib().rt_rsqrt_table_builtin(t.ctypes.data), "rt_rsqrt_table_builtin")
@@ -661,7 +702,8 @@ class Device:
         """What the last trace launched (rt_trace_last_info): segments counted
         but folded analytically (dead tiles), P, tiles traced / total, whether
         the cull pass ran; plus "TileCounts" (rt_trace_last_tile_counts): 1 when the launch took
-        per-tile counts."""
+        per-tile counts, and "DirectionTable" (rt_trace_last_direction_table): 1 when its kernel chose
+        the member entries by the direction table."""
         info = RtTraceInfo()
         _check(lib().rt_trace_last_info(self.handle, ctypes.byref(info)), "rt_trace_last_info")
         out = {n: int(getattr(info, n)) for n, _ in RtTraceInfo._fields_}
@@ -669,6 +711,10 @@ class Device:
         if hasattr(lib(), "rt_trace_last_tile_counts"):  # (an older A/B build, RT_TRACE_LIB, has no such launches)
             _check(lib().rt_trace_last_tile_counts(self.handle, ctypes.byref(tc)), "rt_trace_last_tile_counts")
         out["TileCounts"] = int(tc.value)
+        dt = c_uint32(0)
+        if hasattr(lib(), "rt_trace_last_direction_table"):  # (as above)
+            _check(lib().rt_trace_last_direction_table(self.handle, ctypes.byref(dt)), "rt_trace_last_direction_table")
+        out["DirectionTable"] = int(dt.value)
         return out
 
     def reserve(self, width: int, local_rows: int) -> None:

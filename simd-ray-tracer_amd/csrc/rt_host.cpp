@@ -115,6 +115,7 @@ struct LastLaunch {
     bool empty_capable = false;
     bool folded_on_device = false;  // SegmentsFolded is h_folded's
     bool tile_counts = false;       // the launch took per-tile counts (rt_trace_last_tile_counts)
+    bool dir_table = false;         // its kernel is the direction walk's (rt_trace_last_direction_table)
 };
 
 struct rt_device {
@@ -400,7 +401,7 @@ extern "C" int rt_scene_upload(rt_device *d, const rt_scene *scene) {
     if (!d || !scene) return fail(RT_EINVAL, "rt_scene_upload: NULL argument");
     PackedSet ps[2];
     for (int rs = 0; rs < 2; ++rs) {
-        const int rc = pack_set(scene, rs, ps[rs], d->sw.pf_rel, d->sw.cluster_k, d->sw.sub_spheres);
+        const int rc = pack_set(scene, rs, ps[rs], d->sw.pf_rel, d->sw.cluster_k, d->sw.sub_spheres, d->sw.dir_table != 0);
         if (rc) return rc;
     }
     HIP_OK(hipSetDevice(d->ordinal));
@@ -420,8 +421,20 @@ extern "C" int rt_scene_upload(rt_device *d, const rt_scene *scene) {
             f.n_cpairs = cl.n_cpairs;
             f.cl_words = cl.words;
         }
-        f.clusters_x_ok = false;
-        if (const int rc2 = upload_table(d, b.clusters_x, b.cap_clusters_x, cl.xtab)) return rc2;
+        f.clusters_x_ok = f.dir_table = false;
+        if (cl.dir.empty()) {
+            if (const int rc2 = upload_table(d, b.clusters_x, b.cap_clusters_x, cl.xtab)) return rc2;
+        } else {
+            // the direction block behind the expanded table, its offset in float4 rows in word 3 of the row {c0, .}
+            // (rt_layout.h): one buffer, so the kernel reaches the block from TraceArgs.clusters
+            std::vector<float> both(cl.xtab);
+            const uint32_t at = (uint32_t)(both.size() / 4u);
+            memcpy(&both[3], &at, 4);
+            both.insert(both.end(), cl.dir.begin(), cl.dir.end());
+            if (const int rc2 = upload_table(d, b.clusters_x, b.cap_clusters_x, both)) return rc2;
+            HIP_OK(hipStreamSynchronize(d->stream));  // (`both` is pageable and leaves scope here)
+            f.dir_table = cl.x_ok;
+        }
         f.clusters_x_ok = !cl.xtab.empty() && cl.x_ok;
     }
     HIP_OK(hipStreamSynchronize(d->stream));
@@ -794,6 +807,7 @@ static void record_info(rt_device *d, const rt_trace_desc *desc, const LaunchReq
     l.info.OneWaveGroups = a.solo;
     l.info.Walk = a.walk;
     l.tile_counts = rq.per_tile();
+    l.dir_table = rtk_walk_direction(a, p.cull, p.lpp);
     l.folded_on_device = false;
 }
 
@@ -1119,6 +1133,12 @@ extern "C" int rt_trace_last_info(rt_device *d, rt_trace_info *out) {
 extern "C" int rt_trace_last_tile_counts(rt_device *d, uint32_t *out) {
     if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_tile_counts: NULL argument");
     *out = d->last.tile_counts ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_trace_last_direction_table(rt_device *d, uint32_t *out) {
+    if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_direction_table: NULL argument");
+    *out = d->last.dir_table ? 1u : 0u;
     return RT_OK;
 }
 

@@ -140,11 +140,17 @@ constexpr uint32_t kCullFolded = 130;  // a per-tile launch's folded segments (r
 // 7-op estimate (rtk_walk.h pair_prefilter_x; rt_pack.cpp expand_table).  The host sets
 // the last only where that table exists and is proven and useful for the scene, and only for a
 // launch of a kernel that reads it (below); every other kernel tests the field as a boolean.
-enum { kPrefilterOff = 0, kPrefilterOn = 1, kPrefilterExpanded = 2 };
+// kPrefilterDirection: the expanded table, and behind it in the same buffer the direction block of a one-word
+// table (rt_layout.h; word 3 of the row {c0, .} is its offset): the launch fact of the direction walk below.
+enum { kPrefilterOff = 0, kPrefilterOn = 1, kPrefilterExpanded = 2, kPrefilterDirection = 3 };
+static inline bool rtk_prefilter_expanded(uint32_t prefilter) { return prefilter >= (uint32_t)kPrefilterExpanded; }
 // Secondary-ray walk variants (rtk_shape.h Walk<>): any (run-time dispatch),
 // the per-group loops, or a cluster walk with 1/2/4 pair-mask words and
 // scene-wide or per-lane ("Rel") thresholds
-enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWalkCl2Rel, kWalkCl4Rel };
+enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWalkCl2Rel, kWalkCl4Rel,
+       // kWalkCl1 with the direction table choosing the member entries (rtk_walk.h direction_groups): a kernel of
+       // its own, never a request -- TraceArgs.walk and rt_trace_info.Walk stay kWalkCl1, rtk_walk_kernel picks it
+       kWalkCl1Dir };
 // Compile-time flag of trace_kernel, off in every value above: OR'ed into the kernel's WALK template
 // value it compiles the per-tile counts variant (TraceArgs.tile_counts_at).  A flag bit of an existing
 // parameter rather than a parameter of its own, so that the kernels without it keep their symbols.
@@ -174,6 +180,14 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 //                   of each entry's own E -- rt_pack.cpp expand_table).  A scene-wide table without that
 //                   (a scene placed far from its own extent's scale) is walked by the run-time kernel
 //                   on the table as it always was.
+//   direction table the one-word scene-wide walk (kWalkCl1) has a second kernel, kWalkCl1Dir, which chooses its
+//                   member entries by the direction block behind the expanded table.  It runs where that block
+//                   exists (prefilter == kPrefilterDirection: the expanded table is in use, the host built the
+//                   block -- rt_device_options DirectionTable -- and lays it behind the table), the walk has one
+//                   mask word and the scene at most kDirMaxGroups groups (128 spheres); else kWalkCl1 as before.
+//                   The host offers the block by default to the shapes of at most 8 lanes per pixel
+//                   (rtk_direction_default): the 16-lane shape is the 8-rank band share's, launches of half a
+//                   millisecond, which measured 3.5 % slower with it; DirectionTable on offers it there too.
 // and the kernels exist only for the culled production shapes (rtk_walk_shape).  Every other launch
 // runs the run-time kernel (kWalkAny), which tests each fact where it matters and dispatches the
 // walk the table asks for.
@@ -182,7 +196,7 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 static inline uint32_t rtk_walk_request(const TraceArgs &a, bool walk_any) {
     if (walk_any || !a.fast_sqrt || a.max_bounce == 0u) return kWalkAny;
     if (!a.clusters) return kWalkGroups;
-    if (!a.pf_relative && a.prefilter != (uint32_t)kPrefilterExpanded) return kWalkAny;
+    if (!a.pf_relative && !rtk_prefilter_expanded(a.prefilter)) return kWalkAny;
     if (a.cl_words == 1u) return a.pf_relative ? kWalkCl1Rel : kWalkCl1;
     if (a.cl_words == 2u) return a.pf_relative ? kWalkCl2Rel : kWalkCl2;
     return a.pf_relative ? kWalkCl4Rel : kWalkCl4;
@@ -198,8 +212,11 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
     if (!a.fast_sqrt || a.max_bounce == 0u || a.frames == 0u) return kWalkAny;
     if (a.walk >= (uint32_t)kWalkCl1 && (a.clusters == nullptr || a.n_cpairs == 0u || a.n_groups == 0u || !a.prefilter))
         return kWalkAny;
-    if (a.walk >= (uint32_t)kWalkCl1 && a.walk <= (uint32_t)kWalkCl4 && a.prefilter != (uint32_t)kPrefilterExpanded)
+    if (a.walk >= (uint32_t)kWalkCl1 && a.walk <= (uint32_t)kWalkCl4 && !rtk_prefilter_expanded(a.prefilter))
         return kWalkAny;
+    if (a.walk == (uint32_t)kWalkCl1 && a.prefilter == (uint32_t)kPrefilterDirection && a.cl_words == 1u &&
+        a.n_groups <= kDirMaxGroups)
+        return kWalkCl1Dir;
     // (and the expanded table is read by no other kernel: the host decides with rtk_walk_expanded)
     return a.walk <= (uint32_t)kWalkCl4Rel ? a.walk : (uint32_t)kWalkAny;
 }
@@ -207,7 +224,13 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
 // table, prefilter = kPrefilterExpanded), asks this, and puts the plain table back where the answer is no.
 static inline bool rtk_walk_expanded(const TraceArgs &a, int cull, int lanes_per_pixel) {
     const uint32_t k = rtk_walk_kernel(a, cull, lanes_per_pixel);
-    return k >= (uint32_t)kWalkCl1 && k <= (uint32_t)kWalkCl4;
+    return (k >= (uint32_t)kWalkCl1 && k <= (uint32_t)kWalkCl4) || k == (uint32_t)kWalkCl1Dir;
+}
+// The launch shapes the direction block is offered to without being asked for (rt_plan.cpp route_kernel).
+constexpr bool rtk_direction_default(int lanes_per_pixel) { return lanes_per_pixel <= 8; }
+// Whether it is the direction walk's kernel (rt_trace_last_direction_table).
+static inline bool rtk_walk_direction(const TraceArgs &a, int cull, int lanes_per_pixel) {
+    return rtk_walk_kernel(a, cull, lanes_per_pixel) == (uint32_t)kWalkCl1Dir;
 }
 
 enum { kStatPriIters = 0, kStatPriLanes, kStatSecIters, kStatSecLanes, kStatPriGroups, kStatSecHitGroups,

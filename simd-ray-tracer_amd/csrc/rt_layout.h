@@ -2,6 +2,7 @@
 // sphere records and the clustered prefilter tables.  Plain C++, no HIP: the packer builds as a host
 // program (tests/pack_check).  Internal; not part of include/.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 constexpr uint32_t kGroupF4 = 5;      // float4 rows per sphere group:
@@ -50,6 +51,49 @@ constexpr float kSlabRel = 0x1p-9f;  // the slab test's per-lane margin per unit
 constexpr uint32_t kClMaxGroups = 128;   // table built up to this many groups
 constexpr uint32_t kClAutoGroups = 128;  // used by default up to this many (rt_plan.h Switches.clusters; RTWeekend's
                                          // 121 groups: 11.3k Mrays/s clustered against 9.4k per group)
+
+// The direction table of a one-word scene-wide table (rt_pack.cpp direction_table; rtk_walk.h direction_groups):
+// per sphere slot j and direction cell, the mask of the sphere pairs a ray that leaves ball j in a direction of
+// that cell can be accepted on, in the layout of the wave's pair mask (bit p: spheres 2p, 2p + 1).  Masks are
+// u32 for a scene of at most 32 pairs (16 groups), else u64; row j holds kDirCells of them.
+// In front of the rows lie the member entries in PAIR order: entry p = the member pair {2p, 2p + 1} in the
+// recentred form of the expanded table (the rows of a member pair above, thresholds and behind bounds copied
+// from that table's own entry of each sphere), so that entry p is 4 p rows from the block's start.
+// On the device the block follows the expanded table in the same buffer, and word 3 of that table's first row
+// {c0, .} holds the block's offset from the row in float4 units (0: no block): TraceArgs does not grow.
+// The cell of a direction D with |D|^2 within 2^-16 of 1: the face is D's largest component by magnitude and
+// its sign (x wins ties over y over z), and the two other components a, b -- each at most sqrt((1 + 2^-16)/2) <
+// kDirSpan in magnitude -- index a kDirN x kDirN grid over [-kDirSpan, kDirSpan]^2 as they are: no division, no
+// reciprocal.  Every operation is an IEEE f32 compare, FMA, floor or clamp, so host and device agree bit for
+// bit, and the host bounds a cell by the preimage of the index arithmetic itself (rt_pack.cpp cell_cone).
+#if defined(__HIPCC__)
+#define RT_LAYOUT_HD __host__ __device__
+#else
+#define RT_LAYOUT_HD
+#endif
+constexpr uint32_t kDirN = 16;  // cells per face edge (rt_pack.cpp direction_table has the measurement)
+constexpr uint32_t kDirCells = 6u * kDirN * kDirN;
+constexpr float kDirSpan = 0.7072f;
+constexpr float kDirScale = (float)kDirN / (2.0f * kDirSpan), kDirHalf = 0.5f * (float)kDirN;
+constexpr uint32_t kDirMaxGroups = 32;  // one mask word: at most 128 spheres
+RT_LAYOUT_HD inline uint32_t dir_cell_axis(float v) {
+    const float t = __builtin_floorf(__builtin_fmaf(v, kDirScale, kDirHalf));
+    return (uint32_t)__builtin_fminf(__builtin_fmaxf(t, 0.0f), (float)(kDirN - 1u));
+}
+RT_LAYOUT_HD inline uint32_t dir_cell(float dx, float dy, float dz) {
+    const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
+    const bool fx = ax >= ay && ax >= az, fy = !fx && ay >= az;
+    const float m = fx ? dx : fy ? dy : dz;
+    const float a = fx ? dy : dx, b = (fx || fy) ? dz : dy;
+    const uint32_t face = (fx ? 0u : fy ? 2u : 4u) + (m < 0.0f ? 1u : 0u);
+    return (face * kDirN + dir_cell_axis(a)) * kDirN + dir_cell_axis(b);
+}
+// float4 rows of the block's member entries, and the block's size in floats
+constexpr uint32_t dir_member_f4(uint32_t n_groups) { return 2u * n_groups * cl_entry_f4(1u); }
+constexpr bool dir_mask64(uint32_t n_groups) { return n_groups > 16u; }
+constexpr size_t dir_block_floats(uint32_t n_groups) {
+    return 4u * (size_t)dir_member_f4(n_groups) + 4u * (size_t)n_groups * kDirCells * (dir_mask64(n_groups) ? 2u : 1u);
+}
 
 // HBM layout of an uploaded scene (per rule set):
 //   groups    : n_groups x 5 float4 = {x[4]}, {y[4]}, {z[4]}, {r*r[4]}, {r2p[4]}  (80 B/group)

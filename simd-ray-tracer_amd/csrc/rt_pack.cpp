@@ -655,13 +655,165 @@ void expand_table(const std::vector<Sph> &sp, uint32_t n_ent, uint32_t ef, Clust
     t.x_ok = ok && std::isfinite(c0[0]) && std::isfinite(c0[1]) && std::isfinite(c0[2]);
 }
 
+// Direction table (one-word scene-wide tables with x_ok; rt_layout.h has the layout and the cell function
+// dir_cell, rtk_walk.h direction_groups the walk).  Row j, cell c holds bit i >> 1 for every hittable sphere i
+// that some ray of the premise below can be accepted on; a lane tests the member entries of its row's bits
+// only, so a clear bit must be a proven miss under both rule sets.
+// Premise of a lane that reads row j, cell c: (a) |D|^2 = 1 + k, |k| <= K = 2^-16 (every prefiltered round);
+// (b) c = dir_cell(D); (c) |O - S_j| <= R_j = 1.008 r_j, with S_j, r_j^2 the f32 values of the sphere record.
+// (c) is not assumed of the path: the lane measures it (rtk_walk.h origin_near: |rho_j - cc kOwnCc| < rho_j 2^-6 with
+// cc the FMA value of |RN(S_j - O)|^2, within 3.01u of it, and RN(S_j - O) within u per axis of S_j - O, so
+// |O - S_j|^2 <= r_j^2 (1 + 2^-6) / ((1 - 1.9e-5)(1 - 4u)) < (1.0079 r_j)^2) and reads all-ones where the test fails
+// or rho_j is +inf.  (The width 2^-6: a hit point formed with |D|^2 = 1 + k over a segment of length t lies k t^2
+// off the sphere in squared distance, a few 1e-5 at C2 against r^2 / 64 >= 1e-3.)
+// Origins inside ball j (dielectric paths) are covered: (c) bounds the distance from above only.
+// Cell (cell_cone).  The face fixes the sign and the axis of the major component m, |m| >= |a|, |b| for the two minor
+// ones.  Index i of a minor component v is floor(fma(v, kDirScale, kDirHalf)) clamped to [0, kDirN): the FMA is within
+// half an ulp of a value below 16, 2^-21, of v kDirScale + kDirHalf, i.e. v is within 2^-21 / kDirScale < 5e-8 of
+// [(i - kDirHalf) / kDirScale, (i + 1 - kDirHalf) / kDirScale): the interval is widened by 1e-6 and, for the two end
+// indices the clamp feeds, opened to the bound |v| <= sqrt((1 + K)/2) that |m| >= |v| and (a) give.  Host and device
+// run the same IEEE operations (dir_cell is one function), so there is no other index error to cover.  With
+// m^2 = 1 + k - a^2 - b^2, interval arithmetic over the two intervals and |m| >= min|a|, min|b| gives
+// |m| in [m_lo, m_hi]; an empty range means no direction of (a) reaches the cell, and the cell is all-ones
+// (reachability is no premise).  Otherwise every D of the cell lies within delta = |(ha, hb, hm)| (the three
+// half-widths) of the centre vector Cc, so its angle to Cc is at most alpha = asin(delta / |Cc|) (+ 1e-3 rad for
+// the f64 arithmetic here); delta >= |Cc| makes the cell all-ones.
+// Sphere i != j.  A lane that accepts i has dist_r <= r_i^2 and RN(T_r + X_r) >= eps > 0 (it = T - X or T + X, both
+// rule sets).  With l the exact squared distance of S_i from the lane's line and T* = (S_i - O).D/|D|: the
+// reference-rounded dist_r >= l - 13.3u M_i and C_i = RN(S_i - O) moves S_i by u sqrt(M_i) (cluster_bounds), so
+// X_r^2 <= (r_i^2 - l + 13.4u M_i)(1 + 4u), and T_r is within 4.2u sqrt(M_i)|D| of the exact dot, so
+// T* > -(X_r + 4.3u sqrt(M_i)).  The point of the ray (t >= 0) nearest S_i is at t = max(T*, 0): at T* >= 0 its
+// squared distance is l <= r_i^2 + 13.4u M_i, at T* < 0 it is l + T*^2 <= l + (X_r + 4.3u sqrt(M_i))^2.  Either way
+// the forward ray meets the ball of radius s_i = (sigma_i + 6u sqrt(M_i))(1 + 2^-15) about S_i (sigma_i as in
+// cluster_bounds; the factor covers 4u, the cross term and |D| within 2^-17 of 1).  So D points from a point O of
+// ball(S_j, R_j) to a point P of ball(S_i, s_i): with V = S_i - S_j, L = |V|, P - O = V + w, |w| <= rho = s_i + R_j,
+// and the angle theta between D and V has sin(theta) <= rho / L and cos(theta) > 0 when rho < L: theta <= A =
+// asin(rho / L); L <= rho allows every direction (O may lie inside ball i).
+// Bit i >> 1 is set when theta_c - alpha <= A, theta_c the angle of Cc to V, tested on cosines (A + alpha < pi).
+// rho is inflated by 1e-6.
+// M_i bounds |C_i|^2 over every origin on a scene sphere: the premise every scene-wide table rests on
+// (prefilter_rows, scene_wide_bounds), with the launch fact x_ok's "coordinates below 1024" for its slack.
+// Sphere j itself and its pair partner: the own-pair bit is always set.  A slot that is not hittable, or whose
+// record's rho is not r^2 (own_sphere_rho's range), has an all-ones row.
+// n = 16: C2 (64 spheres) tests 7.7 member entries per secondary round in place of 5 cluster and 8.9 member
+// entries (profiles/r20a_dir_walk_stats.txt); the rows are 6 x 16 x 16 u32 = 6 KB per sphere, 384 KB at C2, and
+// building them takes 21 ms per rule set there, four times cluster_table's 5.5 ms: n = 32 would quadruple both.
+struct CellCone {
+    double x = 0.0, y = 0.0, z = 0.0, cos_a = 1.0, sin_a = 0.0;
+    bool all = true;
+};
+CellCone cell_cone(uint32_t face, uint32_t ia, uint32_t ib) {
+    const double vmax = std::sqrt((1.0 + kK) * 0.5) + 1e-6;
+    double lo[2], hi[2], h[2], c[2], sq_min[2], sq_max[2];
+    const uint32_t idx[2] = {ia, ib};
+    CellCone cone;
+    for (int t = 0; t < 2; ++t) {
+        lo[t] = idx[t] == 0u ? -vmax : ((double)idx[t] - (double)kDirHalf) / (double)kDirScale - 1e-6;
+        hi[t] = idx[t] == kDirN - 1u ? vmax : ((double)idx[t] + 1.0 - (double)kDirHalf) / (double)kDirScale + 1e-6;
+        lo[t] = std::max(lo[t], -vmax);
+        hi[t] = std::min(hi[t], vmax);
+        if (lo[t] > hi[t]) return cone;
+        h[t] = 0.5 * (hi[t] - lo[t]);
+        c[t] = 0.5 * (hi[t] + lo[t]);
+        sq_max[t] = std::max(lo[t] * lo[t], hi[t] * hi[t]);
+        sq_min[t] = lo[t] <= 0.0 && hi[t] >= 0.0 ? 0.0 : std::min(lo[t] * lo[t], hi[t] * hi[t]);
+    }
+    double m_lo = std::sqrt(std::max(0.0, 1.0 - kK - sq_max[0] - sq_max[1]));
+    m_lo = std::max(m_lo, std::sqrt(std::max(sq_min[0], sq_min[1])));
+    const double m_hi = std::sqrt(std::max(0.0, 1.0 + kK - sq_min[0] - sq_min[1]));
+    if (m_hi < m_lo) return cone;
+    const double hm = 0.5 * (m_hi - m_lo), mc = (face & 1u ? -0.5 : 0.5) * (m_hi + m_lo);
+    const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + mc * mc);
+    const double delta = std::sqrt(h[0] * h[0] + h[1] * h[1] + hm * hm);
+    if (!(delta < len)) return cone;
+    const double alpha = std::asin(delta / len) + 1e-3;
+    if (!(alpha < 1.5)) return cone;
+    // dir_cell's axes: face 0/1 major x (a = y, b = z), 2/3 major y (a = x, b = z), 4/5 major z (a = x, b = y)
+    const double a = c[0] / len, b = c[1] / len, m = mc / len;
+    switch (face >> 1) {
+        case 0: cone.x = m, cone.y = a, cone.z = b; break;
+        case 1: cone.x = a, cone.y = m, cone.z = b; break;
+        default: cone.x = a, cone.y = b, cone.z = m; break;
+    }
+    cone.cos_a = std::cos(alpha);
+    cone.sin_a = std::sin(alpha);
+    cone.all = false;
+    return cone;
+}
+
+void direction_table(const std::vector<Sph> &sp, const std::vector<float> &gv, uint32_t n_groups, uint32_t first_member,
+                     uint32_t n_ent, uint32_t ef, ClusterTable &t) {
+    const bool wide = dir_mask64(n_groups);
+    const uint32_t words = wide ? 2u : 1u, n_slots = 4u * n_groups;
+    const size_t rows_at = 4u * (size_t)dir_member_f4(n_groups);
+    t.dir.assign(dir_block_floats(n_groups), 0.0f);
+    // the member entries in pair order, each half copied from the expanded table's own entry of its sphere
+    for (uint32_t p = 0; p < 2u * n_groups; ++p)
+        for (uint32_t h = 0; h < 2u; ++h) t.dir[(size_t)p * ef + cl_threshold(h)] = -INFINITY;
+    const float *xt = t.xtab.data() + 4u;
+    for (uint32_t e = first_member; e < n_ent; ++e)
+        for (uint32_t h = 0; h < 2u; ++h) {
+            const float *src = xt + (size_t)e * ef;
+            if (!std::isfinite(src[cl_threshold(h)])) continue;
+            uint32_t s;
+            memcpy(&s, &src[cl_slot(h)], 4);
+            float *dst = &t.dir[(size_t)(s >> 1) * ef];
+            const uint32_t dh = s & 1u;
+            for (uint32_t ax = 0; ax < 3u; ++ax) dst[cl_centre(ax, dh)] = src[cl_centre(ax, h)];
+            dst[cl_threshold(dh)] = src[cl_threshold(h)];
+            dst[cl_behind(dh)] = src[cl_behind(h)];
+            dst[cl_slot(dh)] = src[cl_slot(h)];
+            memcpy(&dst[cl_bits(0u) + 2u * dh], &src[cl_bits(0u) + 2u * h], 8);
+        }
+    std::vector<CellCone> cones(kDirCells);
+    for (uint32_t c = 0; c < kDirCells; ++c) cones[c] = cell_cone(c / (kDirN * kDirN), c / kDirN % kDirN, c % kDirN);
+    std::vector<uint64_t> row(kDirCells);
+    const uint64_t valid = n_groups == 32u ? ~0ull : (1ull << (2u * n_groups)) - 1ull;  // the pairs there are entries for
+    std::vector<const Sph *> of_slot(n_slots, nullptr);
+    for (const Sph &o : sp) of_slot[o.s] = &o;
+    for (uint32_t j = 0; j < n_slots; ++j) {
+        const Sph *oj = of_slot[j];
+        const bool measured = oj && std::isfinite(t.own_rho[j]);  // (the lane's test of (c) can pass)
+        std::fill(row.begin(), row.end(), measured ? 1ull << (j >> 1) : ~0ull);
+        for (uint32_t c = 0; measured && c < kDirCells; ++c)
+            if (cones[c].all) row[c] = ~0ull;
+        for (size_t ii = 0; measured && ii < sp.size(); ++ii) {
+            const Sph &oi = sp[ii];
+            if (oi.s == j) continue;
+            const uint64_t bit = 1ull << (oi.s >> 1);
+            const double rj = std::sqrt((double)gv[slot_at(j, kRowR2)]) * 1.008;
+            const double vx = oi.x - oj->x, vy = oi.y - oj->y, vz = oi.z - oj->z, len = std::sqrt(vx * vx + vy * vy + vz * vz);
+            const double rho = ((sigma(oi, false) + 6.0 * kU * std::sqrt(oi.m)) * (1.0 + 0x1p-15) + rj) * (1.0 + 1e-6);
+            if (!(rho < len)) {
+                for (uint64_t &m : row) m |= bit;
+                continue;
+            }
+            const double sa = rho / len, ca = std::sqrt(1.0 - sa * sa);
+            const double ux = vx / len, uy = vy / len, uz = vz / len;
+            for (uint32_t c = 0; c < kDirCells; ++c) {
+                const CellCone &k = cones[c];
+                if (k.all) continue;
+                // cos(theta_c) >= cos(A + alpha)
+                if (ux * k.x + uy * k.y + uz * k.z >= ca * k.cos_a - sa * k.sin_a - 1e-9) row[c] |= bit;
+            }
+        }
+        float *out = &t.dir[rows_at + (size_t)j * kDirCells * words];
+        for (uint32_t c = 0; c < kDirCells; ++c) {
+            const uint32_t lo = (uint32_t)(row[c] & valid), hi = (uint32_t)((row[c] & valid) >> 32);
+            put_u(out + (size_t)c * words, lo);
+            if (wide) put_u(out + (size_t)c * words + 1u, hi);
+        }
+    }
+}
+
 // The table of the packed group rows gv (prefilter_rows done).  relative: per-lane thresholds.
 // k_override / sub_override: rt_device_options ClusterCount / SubClusterSpheres (0: per scene).
 // No table (n_cpairs 0; the result is then as constructed, with `words` set and every rho +inf)
 // beyond kClMaxGroups groups and below 8 hittable spheres.  Only a scene-wide table has rho and
-// the expanded table.
+// the expanded table, and only a one-word one whose expanded table is in use the direction block
+// (dir_table: rt_device_options DirectionTable off builds none).
 ClusterTable cluster_table(const std::vector<float> &gv, uint32_t n_groups, bool relative, uint32_t k_override,
-                           uint32_t sub_override) {
+                           uint32_t sub_override, bool dir_table) {
     ClusterTable t;
     t.own_rho.assign(4u * (size_t)n_groups, INFINITY);
     t.words = n_groups <= 32u ? 1u : n_groups <= 64u ? 2u : 4u;
@@ -676,7 +828,9 @@ ClusterTable cluster_table(const std::vector<float> &gv, uint32_t n_groups, bool
     const Counts cnt = lay_out(cs, two_levels, gv, behind_of_slot(sp, n_groups, relative), t.words, relative, t.tab);
     if (!relative) {
         own_sphere_rho(sp, gv, t.own_rho);
-        expand_table(sp, cnt.cp + cnt.sp + cnt.mp, cl_entry_f4(t.words, relative) * 4u, t);
+        const uint32_t n_ent = cnt.cp + cnt.sp + cnt.mp, ef = cl_entry_f4(t.words, relative) * 4u;
+        expand_table(sp, n_ent, ef, t);
+        if (dir_table && t.x_ok && t.words == 1u) direction_table(sp, gv, n_groups, cnt.cp + cnt.sp, n_ent, ef, t);
     }
     t.n_cpairs = cnt.cp;
     t.levels = two_levels ? 2u : 1u;
@@ -686,7 +840,8 @@ ClusterTable cluster_table(const std::vector<float> &gv, uint32_t n_groups, bool
 
 }  // namespace
 
-int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env, uint32_t cluster_k, uint32_t sub_spheres) {
+int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env, uint32_t cluster_k, uint32_t sub_spheres,
+             bool dir_table) {
     const uint32_t ng = scene->SIMDSpheres.Count;
     const uint32_t ns = scene->ScalarSpheres.Count;
     if (ng == 0 || !scene->SIMDSpheres.Data || !scene->Materials.Data || ns == 0 || !scene->ScalarSpheres.Data)
@@ -736,7 +891,7 @@ int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env, uint32
     // (rtk_walk.h kPfRel, kClRel): the cluster table is built for that rule, and
     // the threshold row (kRowR2P) then holds r^2 (-inf: never hit).
     p.relative = pf_rel_env == 1 || (pf_rel_env < 0 && !p.prefilter_pays);
-    p.cl = cluster_table(gv, n, p.relative, cluster_k, sub_spheres);
+    p.cl = cluster_table(gv, n, p.relative, cluster_k, sub_spheres, dir_table);
     // (a record per real sphere of the scalar set, per slot of the SIMD set; without a table every rho is +inf)
     for (uint32_t sl = 0; sl < (rs == 0 ? 4u * n : ns); ++sl) p.mats[(size_t)sl * 4u * kSphereF4 + 3u] = p.cl.own_rho[sl];
     if (p.relative)
@@ -748,9 +903,11 @@ int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env, uint32
 // ---------------------------------------------------------------------------------------------
 // The queries of include/rt_trace.h: what rt_scene_upload derives for one rule set at the default
 // options, no device involved.  Each checks its arguments and packs the rule set:
-static int query(const char *who, bool args_ok, const rt_scene *scene, uint32_t enable_simd, PackedSet &p) {
+// (only rt_scene_direction_table builds the direction block)
+static int query(const char *who, bool args_ok, const rt_scene *scene, uint32_t enable_simd, PackedSet &p,
+                 bool dir_table = false) {
     if (!args_ok) return rt_fail(RT_EINVAL, "%s: NULL argument", who);
-    return pack_set(scene, enable_simd ? 0 : 1, p);
+    return pack_set(scene, enable_simd ? 0 : 1, p, -1, 0, 0, dir_table);
 }
 
 extern "C" int rt_scene_prefilter(const rt_scene *scene, uint32_t enable_simd, float *out_r2, float *out_r2p,
@@ -834,3 +991,39 @@ extern "C" int rt_scene_cluster_layout(const rt_scene *scene, uint32_t enable_si
     *out_sub_pairs = p.cl.sub_pairs;
     return RT_OK;
 }
+
+extern "C" int rt_scene_direction_table(const rt_scene *scene, uint32_t enable_simd, void *out, uint64_t capacity_bytes,
+                                        uint64_t *out_bytes, rt_direction_table_info *info) {
+    PackedSet p;
+    if (const int rc = query("rt_scene_direction_table", scene && out_bytes && info, scene, enable_simd, p, true)) return rc;
+    const bool have = !p.cl.dir.empty();
+    const size_t rows_at = have ? 4u * (size_t)dir_member_f4(p.n_groups) : 0u;
+    const uint64_t bytes = have ? (uint64_t)(p.cl.dir.size() - rows_at) * 4u : 0u;
+    *out_bytes = bytes;
+    info->CellsPerEdge = have ? kDirN : 0u;
+    info->MaskBits = have ? (dir_mask64(p.n_groups) ? 64u : 32u) : 0u;
+    info->Rows = have ? 4u * p.n_groups : 0u;
+    info->CellsPerRow = have ? kDirCells : 0u;
+    if (out && bytes) {
+        if (capacity_bytes < bytes)
+            return rt_fail(RT_EINVAL, "rt_scene_direction_table: capacity %llu < %llu", (unsigned long long)capacity_bytes,
+                           (unsigned long long)bytes);
+        memcpy(out, p.cl.dir.data() + rows_at, (size_t)bytes);
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_direction_members(const rt_scene *scene, uint32_t enable_simd, float *out, uint32_t capacity_f4,
+                                          uint32_t *out_f4) {
+    PackedSet p;
+    if (const int rc = query("rt_scene_direction_members", scene && out_f4, scene, enable_simd, p, true)) return rc;
+    const uint32_t nf4 = p.cl.dir.empty() ? 0u : dir_member_f4(p.n_groups);
+    *out_f4 = nf4;
+    if (out && nf4) {
+        if (capacity_f4 < nf4) return rt_fail(RT_EINVAL, "rt_scene_direction_members: capacity %u < %u", capacity_f4, nf4);
+        memcpy(out, p.cl.dir.data(), (size_t)nf4 * 16u);
+    }
+    return RT_OK;
+}
+
+extern "C" uint32_t rt_direction_cell(float dx, float dy, float dz) { return dir_cell(dx, dy, dz); }

@@ -23,6 +23,9 @@ struct ClusterTable {
     uint32_t levels = 0;         // 1 or 2 (words >= 2); 0: no table
     uint32_t sub_pairs = 0;      // sub-cluster pair entries of a two-level table
     bool x_ok = false;           // xtab proven and useful (the launch fact kPrefilterExpanded)
+    // the direction block of a one-word scene-wide table with x_ok (rt_layout.h; rt_pack.cpp direction_table):
+    // member entries in pair order, then the mask rows as bit patterns; empty: none
+    std::vector<float> dir;
 };
 
 // One rule set of a scene: rs 0 = SIMD rules from SIMDSpheres (main.cpp:399-400) + Materials[4g+l]
@@ -39,6 +42,6 @@ struct PackedSet {
 };
 
 // pf_rel_env, cluster_k, sub_spheres (rt_plan.h Switches): rt_device_options PrefilterRelative (-1 auto, 0 never, 1 always),
-// ClusterCount and SubClusterSpheres (0: per scene)
+// ClusterCount and SubClusterSpheres (0: per scene); dir_table: DirectionTable (off builds no direction block)
 int pack_set(const rt_scene *scene, int rs, PackedSet &p, int pf_rel_env = -1, uint32_t cluster_k = 0,
-             uint32_t sub_spheres = 0);
+             uint32_t sub_spheres = 0, bool dir_table = false);

@@ -15,7 +15,7 @@ int check_options(const rt_device_options *o) {
     const int32_t tri[] = {o->Cull, o->Prefilter, o->PrefilterRelative, o->Clusters, o->OneWaveGroups,
                            o->SphereSourceLds, o->SceneInHbm, o->TablesInLds, o->WalkAny, o->Interleave,
                            o->MergeRounds, o->TileOrder, o->WaveOrder, o->PixelSort, o->XcdGroup,
-                           o->SplitFirstLaunch, o->EncodePass};
+                           o->SplitFirstLaunch, o->EncodePass, o->DirectionTable};
     for (const int32_t v : tri)
         if (v < -1 || v > 1) return rt_fail(RT_EINVAL, "rt_device_options: a switch is %d (RT_OPT_DEFAULT/ON/OFF)", v);
     const int32_t lpp = o->LanesPerPixel;
@@ -63,6 +63,7 @@ Switches from_options(const rt_device_options &o) {
     if (o.SplitGrowth) s.split_growth = (uint32_t)o.SplitGrowth;
     if (o.OrderLaunches) s.order_launches = o.OrderLaunches < 0 ? 0u : (uint32_t)o.OrderLaunches;
     s.cur_pass = on(o.EncodePass, true) ? 1u : 0u;
+    s.dir_table = o.DirectionTable == RT_OPT_DEFAULT ? 1 : o.DirectionTable == RT_OPT_ON ? 2 : 0;
     return s;
 }
 
@@ -290,7 +291,9 @@ static void route_kernel(const Switches &sw, const SceneFacts &sf, int lpp, bool
         // kPrefilterExpanded): offered here, and taken back unless this launch's kernel is one of them.
         if (a.clusters && !a.pf_relative && sf.clusters_x_ok && !sw.walk_any) {
             a.clusters = tables.expanded;  // (the row {c0, 0}, then entry 0)
-            a.prefilter = kPrefilterExpanded;
+            // (with the direction block behind it where the upload built one: rtk_walk_kernel decides the rest)
+            const bool dir = sf.dir_table && (sw.dir_table == 2 || rtk_direction_default(lpp));
+            a.prefilter = dir ? kPrefilterDirection : kPrefilterExpanded;
             p.table = kTableExpanded;
             a.walk = rtk_walk_request(a, false);
             if (!rtk_walk_expanded(a, sw.cull != 0, lpp)) {

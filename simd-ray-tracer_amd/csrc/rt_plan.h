@@ -71,6 +71,10 @@ struct Switches {
     // sorting ones after two warm-ups
     uint32_t order_launches = 4;
     uint32_t cluster_k = 0, sub_spheres = 0;  // cluster_table's K and sub-cluster size (0: per scene)
+    // options DirectionTable off (0): rt_scene_upload builds no direction block, so every one-word scene-wide launch
+    // runs the cluster walk (kWalkCl1) as before (A/B and the parity variants); default 1: the direction walk for
+    // the shapes of rtk_direction_default; on (2): for every shape with walk kernels
+    int dir_table = 1;
 };
 
 // What rt_device_create_ex refuses in its options (o == NULL: nothing), before anything touches a device.
@@ -87,6 +91,7 @@ struct SceneFacts {
     uint32_t n_cpairs = 0;       // 0: per-group prefilter loop
     uint32_t cl_words = 0;
     bool clusters_x_ok = false;  // the expanded table is proven and useful for the scene (kPrefilterExpanded)
+    bool dir_table = false;      // the direction block lies behind the expanded table (kPrefilterDirection)
     // of the scene, the same in both rule sets' facts
     uint32_t n_spheres = 0;
     bool use_sky = false;

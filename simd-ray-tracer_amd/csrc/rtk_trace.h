@@ -478,6 +478,7 @@ void trace_kernel(TraceArgs a) {
     // Q > 1 lane moving to its next pixel slot) carries none over.
     float pend_t = 0.0f;
     uint32_t pend_s = 0u;
+    uint32_t dir_row = kOwnNone;  // (kWalkCl1Dir: written by shade_hit, read by the same round's walk)
     // Re-derive the winner's HitNormal / NextRayOrigin exactly as they were
     // formed at acceptance (main.cpp:423-429), then shade and bounce.
     // Returns the slot the continued ray leaves and cannot accept (rtk_walk.h own_sphere: formed from the
@@ -505,6 +506,8 @@ void trace_kernel(TraceArgs a) {
             // made opaque so that the two loads stay two)
             uint32_t again = sidx;
             asm volatile("" : "+v"(again));
+            // (the direction walk's kernel: the row of its table this lane reads -- rtk_walk.h direction_groups)
+            if constexpr (Walk<WALK>::DIR) dir_row = origin_near(p, mat_src[kSphereF4 * again]) ? sidx : kOwnNone;
             return own_sphere(p, mat_src[kSphereF4 * again], sidx);
         } else {
             return kOwnNone;
@@ -714,7 +717,9 @@ void trace_kernel(TraceArgs a) {
                         if (do_sec && !pf) st.exact_round(u2);
                         if (SRC == kSrcSmem && pf && (Walk<WALK>::CLUSTERS || a.n_cpairs)) {
                             PfStats *ps = st.pf_round();
-                            if constexpr (Walk<WALK>::CLUSTERS) {
+                            if constexpr (Walk<WALK>::DIR) {
+                                direction_groups<SIMD>(a, ray, h, fast, own, dir_row, ps);
+                            } else if constexpr (Walk<WALK>::CLUSTERS) {
                                 // (the scene-wide walk kernels hold the expanded prefilter: rtk_walk.h pair_prefilter_x)
                                 clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL, !Walk<WALK>::REL>(a, lds_groups, ray, h, fast,
                                                                                                             own, ps);
@@ -902,6 +907,7 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
         case kWalkCl1Rel: RTK_LAUNCH_SOLO(S, true, kWalkCl1Rel); return;      \
         case kWalkCl2Rel: RTK_LAUNCH_SOLO(S, true, kWalkCl2Rel); return;      \
         case kWalkCl4Rel: RTK_LAUNCH_SOLO(S, true, kWalkCl4Rel); return;      \
+        case kWalkCl1Dir: RTK_LAUNCH_SOLO(S, true, kWalkCl1Dir); return;      \
         default: break;                                                       \
     }
             if (simd) { RTK_WALKS(true) } else { RTK_WALKS(false) }

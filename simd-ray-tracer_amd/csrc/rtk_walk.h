@@ -799,6 +799,106 @@ __device__ __forceinline__ void clustered_groups(const TraceArgs &a, const float
     }
 }
 
+// The direction walk (kWalkCl1Dir: one-word scene-wide tables; rt_pack.cpp direction_table proves it, rt_layout.h
+// has the block's layout).  In place of the cluster level -- five cluster-pair entries and the member entries of
+// every cluster some lane may reach -- each lane of the round reads the pair mask of (the sphere its ray leaves,
+// the cell of its direction), the wave ORs the masks of the round's lanes, and only the member entries of that
+// union run the member test, entry p of the block being the sphere pair p.  The table only chooses the entries:
+// the member test (near line, behind, own sphere), the wave mask it builds and the recheck in group order are
+// those of member_pairs<1, false, true> and clustered_groups.  A pair outside a lane's mask is a proven miss for
+// that lane, a pair outside the union one for every lane of the round, so the wave mask loses only pairs no lane
+// of the round can accept and every accepted candidate is what it was.
+// row: the slot the lane's ray leaves where the lane has measured that its origin lies on that sphere
+// (origin_near), else kOwnNone: the lane then asks for every pair.
+// The table's premise (c): |O - S_j| <= 1.008 r_j, measured as own_sphere measures its own rule, on the same
+// cc (the compiler forms it once): |RN(rho_j - cc kOwnCc)| < RN(rho_j 2^-6); false for rho_j = +inf or NaN.
+__device__ __forceinline__ bool origin_near(const Sample &p, float4 sc) {
+    const float cx = sc.x - p.rx.x, cy = sc.y - p.ry.x, cz = sc.z - p.rz.x;
+    const float cc = __builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz));
+    return __builtin_fabsf(__builtin_fmaf(cc, -kOwnCc, sc.w)) < sc.w * 0x1p-6f;
+}
+
+// The OR of v over the active lanes, in an SGPR: the lowest lane with bits still missing from the union adds
+// its word until none has any (a round's lanes leave about one sphere and share few cells, so a few trips;
+// each lane's own-pair bit is set, so at least one).  trips: the diagnostic build's count.
+__device__ __forceinline__ uint32_t wave_or(uint32_t v, uint32_t &trips) {
+    uint32_t u = 0u;
+    for (;;) {
+        const uint64_t b = __builtin_amdgcn_ballot_w64(v != 0u);
+        if (b == 0ull) break;
+        u |= (uint32_t)__builtin_amdgcn_readlane((int)v, (int)__builtin_ctzll(b));
+        v &= ~u;
+        trips += 1u;
+    }
+    return u;
+}
+
+// ps (RTK_STATS): groups += member entries tested, near_entries as in member_pairs, pairs += sphere pairs
+// rechecked exactly, lane_pairs += trips of the union loop; no cluster entry is tested, and the two cluster
+// counters count the origin measurement instead: cl_top_entered += rounds with a lane that asks for every pair,
+// cl_tested += such lanes.
+template <bool SIMD>
+__device__ __forceinline__ void direction_groups(const TraceArgs &a, const RayPk &ray, Hit &h, bool fast, uint32_t own,
+                                                 uint32_t row, PfStats *ps) {
+    const v4f_t c0 = *(cv4f_t *)a.clusters;
+    const uint32_t at = __float_as_uint(c0.w);  // the block's offset in rows (rt_layout.h)
+    cv4f_t *members = (cv4f_t *)a.clusters + at;
+    const uint32_t n_pairs = 2u * a.n_groups;
+    const uint64_t every = n_pairs >= 64u ? ~0ull : (1ull << n_pairs) - 1ull;  // the pairs there are entries for
+    // the lane's mask: row < 4 n_groups (a sphere the lane has hit) and cell < kDirCells (dir_cell clamps)
+    const bool near = row != kOwnNone;
+    // (the clamp costs one instruction and keeps the gather inside the table whatever a lane carries)
+    const uint32_t idx = (near ? min(row, 4u * a.n_groups - 1u) : 0u) * kDirCells + dir_cell(ray.x.y, ray.y.y, ray.z.y);
+    const uint32_t *rows = (const uint32_t *)(a.clusters + at + dir_member_f4(a.n_groups));
+    uint32_t lo, hi = 0u, trips = 0u;
+    const bool wide = dir_mask64(a.n_groups);  // (wave-uniform)
+    if (wide) {
+        const uint2 m = ((const uint2 *)rows)[idx];
+        lo = m.x;
+        hi = m.y;
+    } else {
+        lo = rows[idx];
+    }
+    if (!near) lo = (uint32_t)every, hi = (uint32_t)(every >> 32);
+    const RayX rx = ray_expand(ray, c0);
+    uint64_t todo = wave_or(lo, trips);
+    if (wide) todo |= (uint64_t)wave_or(hi, trips) << 32;
+    if (ps) {
+        const uint64_t far = __builtin_amdgcn_ballot_w64(!near);
+        ps->lane_pairs += trips, ps->groups += (uint32_t)__builtin_popcountll(todo);
+        ps->cl_top_entered += far != 0ull ? 1u : 0u, ps->cl_tested += (uint32_t)__builtin_popcountll(far);
+    }
+    uint64_t wave = 0ull;
+    while (todo) {
+        const uint32_t pr = (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        // (member_pairs<1, false, true>'s body on entry pr)
+        const Rows4 er = load_rows4(cl_entry(members, pr * (16u * cl_entry_f4(1u))));
+        const v4f_t r0 = er.r0, r1 = er.r1, r2 = er.r2, r3 = er.r3;
+        f2 T;
+        const f2 v = pair_prefilter_x(rx, f2{r0.x, r0.y}, f2{r0.z, r0.w}, f2{r1.x, r1.y}, T);
+        const uint64_t n0m = __builtin_amdgcn_ballot_w64(!(v.x >= r1.z)), n1m = __builtin_amdgcn_ballot_w64(!(v.y >= r1.w));
+        if (ps) ps->near_entries += (n0m | n1m) != 0 ? 1u : 0u;
+        if (!any_lane(n0m, n1m)) continue;
+        const uint64_t w0 = (uint64_t)__float_as_uint(r2.x) | ((uint64_t)__float_as_uint(r2.y) << 32);
+        const uint64_t w1 = (uint64_t)__float_as_uint(r2.z) | ((uint64_t)__float_as_uint(r2.w) << 32);
+        merge_word1(wave, n0m, __builtin_amdgcn_ballot_w64(!(T.x < r3.x)),
+                    __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.z)), w0, n1m,
+                    __builtin_amdgcn_ballot_w64(!(T.y < r3.y)), __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.w)), w1);
+    }
+    // (clustered_groups' recheck of a one-word mask)
+    cv4f_t *gp = (cv4f_t *)a.groups;
+    while (wave) {
+        const uint32_t q = (uint32_t)__builtin_ctzll(wave) & ~1u;
+        const uint32_t g = q >> 1;
+        const uint32_t pp = (uint32_t)(wave >> q);
+        const bool f01 = (pp & 1u) != 0u, f23 = (pp & 2u) != 0u;
+        wave &= ~(3ull << q);
+        if (ps) ps->pairs += (f01 ? 1u : 0u) + (f23 ? 1u : 0u);
+        recheck_pairs<SIMD>(a, load_group_exact_at(gp + kGroupF4 * g), g, ray, h, fast, f01, f23);
+    }
+}
+
 // All four spheres of group g; one wave-level branch per group, nested
 // branches only for the (rare) lanes that pass the distance test.
 template <bool SIMD>
