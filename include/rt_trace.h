@@ -550,6 +550,72 @@ int rt_trace_first_hit(rt_device *dev, const rt_camera_info *cam, const rt_trace
                        const uint32_t *tiles, uint32_t n_tiles, uint32_t flags,
                        const rt_first_hit_planes *out, void *stream);
 
+/* ------------------------------------------------- a filter over the first-hit planes */
+
+#define RT_DENOISE_DEMODULATE 1u   /* divide by the first hit's albedo before, multiply back after */
+#define RT_DENOISE_SRGB_POW   2u   /* Rgba8 through the exact-pow branch, as RT_FLAG_SRGB_POW        */
+#define RT_DENOISE_MAX_ITERATIONS 8u
+
+typedef struct rt_denoise_desc {
+    uint32_t Size;                 /* sizeof(rt_denoise_desc)                                        */
+    uint32_t Width, Height;        /* rt_tile_count(Width, Height) != 0                              */
+    uint32_t Iterations;           /* 1..8 passes; pass i (from 0) samples at step 2^i               */
+    uint32_t Flags;
+    uint32_t NormalPower;          /* 0: no normal stop; k in 1..8: max(0, Np.Nq)^(2^k)              */
+    float    SigmaDepth;           /* 0: no depth stop; else relative to the centre's T; finite, >0  */
+    float    SigmaColor;           /* 0: no colour stop; else luminance width of pass 0, halved per pass */
+    const float        *Mean;      /* DEVICE v4 f32, Width*Height, 16-byte aligned (PreviousImage)   */
+    const rt_first_hit *Hit;       /* DEVICE, 8-byte aligned, required                               */
+    const float        *Normal;    /* DEVICE v4 f32, required when NormalPower != 0, else may be NULL */
+    const float        *Albedo;    /* DEVICE v4 f32, required with RT_DENOISE_DEMODULATE             */
+    float              *Out;       /* DEVICE v4 f32, required                                        */
+    float              *Scratch;   /* DEVICE v4 f32, required when Iterations >= 2                   */
+    uint32_t           *Rgba8;     /* DEVICE or NULL: ColorFromV4(LinearToSRGB(Out))                 */
+} rt_denoise_desc;
+
+/* An edge-avoiding a-trous filter of a running mean (rt_trace's PreviousImage) guided by rt_trace_first_hit's
+ * planes of the same frame.  New; the reference has no filter.  Like rt_encode_rgba8 and rt_tile_delta_rgba8 the
+ * pass needs no rt_device, keeps no state, allocates nothing and does not wait on the host: one kernel launch
+ * per pass on `stream` (NULL: the null stream) of the current HIP device, alternating between Scratch and Out so
+ * that the last pass lands in Out (Iterations == 1: Mean -> Out, Scratch is never touched).  The inputs are only
+ * read; no byte outside Out, Scratch (when used) and Rgba8 (when given) is written.
+ *
+ * The result is defined operation by operation; every operation is one IEEE f32 operation (no contraction,
+ * IEEE division, denormals kept), so it is one set of bits (tests/denoise_ref.py restates it in numpy):
+ *    K = {1/16, 1/4, 3/8, 1/4, 1/16};  lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z;
+ *    pos(v) = v > 0 ? v : 0 (NaN gives 0);  ic0 = 1.0f / SigmaColor, once on the host;
+ *    pass i: s = 1 << i, ic = ic0 * (float)s.  I_0 = Mean; with RT_DENOISE_DEMODULATE I_0.ch = Mean.ch / a.ch,
+ *    a.ch = Albedo.ch > 0.01f ? Albedo.ch : 0.01f where Albedo.w == 1 and a = 1 elsewhere (a miss).
+ *  - Centre p = (x, y): kp = Hit[p].Key, tp = Hit[p].T, lp = lum(I_i[p]); rz = 1.0f / (SigmaDepth * tp), formed
+ *    only when SigmaDepth > 0 and kp != RT_HIT_MISS.
+ *  - acc = (+0, +0, +0), ws = +0.  Taps dy = -2..2 (outer), dx = -2..2 (inner) at q = (x + dx*s, y + dy*s); a
+ *    tap outside the image is skipped.  w = K[dy+2] * K[dx+2]; the centre tap keeps that w.  Any other tap:
+ *      Hit[q].Key != kp (the whole word, RT_HIT_INSIDE included): skipped.
+ *      kp != RT_HIT_MISS and NormalPower = k > 0: d = pos((Np.x*Nq.x + Np.y*Nq.y) + Np.z*Nq.z), k times d = d*d,
+ *        w = w*d.
+ *      kp != RT_HIT_MISS and SigmaDepth > 0: w = w * pos(1.0f - fabsf(tp - Hit[q].T) * rz).
+ *      SigmaColor > 0, hits and misses alike: w = w * pos(1.0f - fabsf(lp - lum(I_i[q])) * ic).
+ *    A tap whose w is not > 0 is skipped (so an infinite or NaN neighbour never enters a pixel it does not
+ *    belong to); otherwise acc.ch = acc.ch + w * I_i[q].ch per channel and ws = ws + w.
+ *  - I_{i+1}[p].ch = acc.ch / ws (the centre gives ws >= 9/64); I_{i+1}[p].w = Mean[p].w.
+ *  - After the last pass the demodulated variant multiplies back, Out.ch = I_n.ch * a.ch, and Rgba8[p] is the
+ *    RGBA8 of Out.xyz as rt_trace and rt_encode_rgba8 encode it (RT_DENOISE_SRGB_POW: the exact-pow branch).
+ * The falloffs are tents, not exponentials: no transcendental, so one result.
+ *
+ * RT_EINVAL, with an rt_last_error text and before anything is enqueued: a NULL desc or a wrong Size; a size
+ * for which rt_tile_count is 0; Iterations outside 1..8; an unknown flag bit; NormalPower > 8; a sigma that is
+ * negative, NaN or infinite; a required pointer that is NULL; a misaligned plane (Mean, Normal, Albedo, Out,
+ * Scratch 16 bytes, Hit 8, Rgba8 4); two of Mean, Out and Scratch that are the same pointer. */
+int rt_denoise(const rt_denoise_desc *desc, void *stream);
+/* Fills *out with Size, Width = Height = 0, Flags = 0, every pointer NULL and the library's defaults:
+ * Iterations = 3 (steps 1, 2, 4: a 29 x 29 footprint), NormalPower = 2 (max(0, Np.Nq)^4), SigmaDepth = 0.25f
+ * (a tap's weight reaches 0 where its depth differs by a quarter of the centre's), SigmaColor = 0.5f (a tap's
+ * weight reaches 0 at a luminance difference of 0.5 in pass 0, 0.25 in pass 1, 0.125 in pass 2: the built-in
+ * scenes are mirrors and glass, whose reflections a filter without a colour stop blurs into a larger error
+ * than the noise it removes).  Chosen on the CPU restatement over 4-spp frames of the three built-in scenes
+ * against their 1024-spp means (DESIGN.md has the table).  RT_EINVAL for NULL. */
+int rt_denoise_defaults(rt_denoise_desc *out);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call

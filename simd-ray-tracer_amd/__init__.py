@@ -137,6 +137,16 @@ first_hit_dtype = np.dtype([("Key", "<u4"), ("T", "<f4")])
 HIT_MISS, HIT_INSIDE, HIT_PIXEL_CENTRE = 0xFFFFFFFF, 0x80000000, 1
 
 
+class RtDenoiseDesc(ctypes.Structure):  # rt_denoise_desc: one rt_denoise call, 88 B
+    _fields_ = [("Size", c_uint32), ("Width", c_uint32), ("Height", c_uint32), ("Iterations", c_uint32),
+                ("Flags", c_uint32), ("NormalPower", c_uint32), ("SigmaDepth", c_float), ("SigmaColor", c_float),
+                ("Mean", c_void_p), ("Hit", c_void_p), ("Normal", c_void_p), ("Albedo", c_void_p), ("Out", c_void_p),
+                ("Scratch", c_void_p), ("Rgba8", c_void_p)]
+
+
+DENOISE_DEMODULATE, DENOISE_SRGB_POW, DENOISE_MAX_ITERATIONS = 1, 2, 8
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -228,6 +238,8 @@ SIGNATURES = {
     "rt_tile_counts_step": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(RtTileRule), c_void_p, c_void_p]),
     "rt_trace_first_hit": (c_int, [c_void_p, POINTER(RtCameraInfo), POINTER(RtTraceDesc), c_void_p, c_uint32, c_uint32,
                                    POINTER(RtFirstHitPlanes), c_void_p]),
+    "rt_denoise": (c_int, [POINTER(RtDenoiseDesc), c_void_p]),
+    "rt_denoise_defaults": (c_int, [POINTER(RtDenoiseDesc)]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -918,6 +930,48 @@ def tile_delta_rgba8(old_ptr: int, new_ptr: int, width: int, height: int, delta_
     16-byte aligned; view a copy with tile_delta_dtype).  Traces nothing."""
     _check(lib().rt_tile_delta_rgba8(c_void_p(old_ptr), c_void_p(new_ptr), width, height, c_void_p(delta_ptr),
                                      c_void_p(stream or 0)), "rt_tile_delta_rgba8")
+
+
+def denoise_defaults() -> dict:
+    """rt_denoise_defaults: the library's Iterations, NormalPower, SigmaDepth and SigmaColor."""
+    d = RtDenoiseDesc()
+    _check(lib().rt_denoise_defaults(ctypes.byref(d)), "rt_denoise_defaults")
+    assert d.Size == ctypes.sizeof(RtDenoiseDesc)
+    return dict(iterations=d.Iterations, normal_power=d.NormalPower, sigma_depth=d.SigmaDepth, sigma_color=d.SigmaColor)
+
+
+def denoise(width: int, height: int, mean_ptr: int, hit_ptr: int, out_ptr: int, scratch_ptr: int = 0,
+            normal_ptr: int = 0, albedo_ptr: int = 0, rgba8_ptr: int = 0, iterations: Optional[int] = None,
+            normal_power: Optional[int] = None, sigma_depth: Optional[float] = None,
+            sigma_color: Optional[float] = None, demodulate: bool = False, srgb_pow: bool = False,
+            stream: Optional[int] = None) -> None:
+    """rt_denoise: the edge-avoiding a-trous filter of the device running mean `mean_ptr` (width * height v4 f32)
+    guided by Device.trace_first_hit's planes of the same frame (`hit_ptr` always; `normal_ptr` when the normal
+    stop is on; `albedo_ptr` with `demodulate`), into `out_ptr` and, when non-zero, its RGBA8 into `rgba8_ptr`.
+    `scratch_ptr` (another width * height v4 f32) is needed from two iterations on.  iterations, normal_power,
+    sigma_depth, sigma_color: None takes the library's default (denoise_defaults()); 0 turns a stop off.
+    Enqueued on `stream`; needs no Device.  ValueError for a count or a width no call can take, RtError for
+    what the library refuses."""
+    dflt = denoise_defaults()
+    it = dflt["iterations"] if iterations is None else iterations
+    k = dflt["normal_power"] if normal_power is None else normal_power
+    sd = dflt["sigma_depth"] if sigma_depth is None else sigma_depth
+    sc = dflt["sigma_color"] if sigma_color is None else sigma_color
+    for name, v, hi in (("iterations", it, DENOISE_MAX_ITERATIONS), ("normal_power", k, 8)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+            raise ValueError(f"denoise: {name} must be an integer of at most {hi}, got {v!r}")
+    if int(it) < 1:
+        raise ValueError("denoise: iterations must be at least 1")
+    for name, v in (("sigma_depth", sd), ("sigma_color", sc)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float("inf"):
+            raise ValueError(f"denoise: {name} must be a finite number >= 0, got {v!r}")
+        if float(v) > float(np.finfo(np.float32).max):
+            raise ValueError(f"denoise: {name} {v!r} is not a finite f32")
+    flags = (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_SRGB_POW if srgb_pow else 0)
+    d = RtDenoiseDesc(ctypes.sizeof(RtDenoiseDesc), width, height, int(it), flags, int(k), float(sd), float(sc),
+                      mean_ptr or None, hit_ptr or None, normal_ptr or None, albedo_ptr or None, out_ptr or None,
+                      scratch_ptr or None, rgba8_ptr or None)
+    _check(lib().rt_denoise(ctypes.byref(d), c_void_p(stream or 0)), "rt_denoise")
 
 
 # ------------------------------------------------- OnInit / OnRender mirror

@@ -1111,6 +1111,47 @@ extern "C" int rt_tile_delta_rgba8(const uint32_t *d_old, const uint32_t *d_new,
     return RT_OK;
 }
 
+// The a-trous filter over the first-hit planes (rt_denoise.hip): the plan's passes (rt_plan.cpp), one launch
+// each.  No device handle, no state, no allocation, no wait.
+extern "C" int rt_denoise(const rt_denoise_desc *desc, void *stream) {
+    DenoisePlan plan;
+    if (const int rc = plan_denoise(desc, plan)) return rc;
+    const bool demodulate = (desc->Flags & RT_DENOISE_DEMODULATE) != 0u;
+    for (uint32_t i = 0; i < plan.n_passes; ++i) {
+        const bool last = i + 1u == plan.n_passes;
+        DenoiseArgs a;
+        a.src = plan.pass[i].src;
+        a.dst = plan.pass[i].dst;
+        a.hit = desc->Hit;
+        a.normal = desc->Normal;
+        a.albedo = desc->Albedo;
+        a.rgba8 = last ? desc->Rgba8 : nullptr;
+        a.width = desc->Width;
+        a.height = desc->Height;
+        a.step = plan.pass[i].step;
+        a.normal_power = desc->NormalPower;
+        a.sigma_depth = desc->SigmaDepth;
+        a.ic = plan.pass[i].ic;
+        a.demod_in = demodulate && i == 0u ? 1u : 0u;
+        a.remod_out = demodulate && last ? 1u : 0u;
+        a.srgb_pow = (desc->Flags & RT_DENOISE_SRGB_POW) ? 1u : 0u;
+        if (rtk_launch_denoise_pass(&a, (hipStream_t)stream) != 0)
+            return fail(RT_EIO, "rt_denoise: launch of pass %u failed: %s", i, hipGetErrorString(hipGetLastError()));
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_denoise_defaults(rt_denoise_desc *out) {
+    if (!out) return fail(RT_EINVAL, "rt_denoise_defaults: NULL argument");
+    memset(out, 0, sizeof(*out));
+    out->Size = (uint32_t)sizeof(*out);
+    out->Iterations = 3u;
+    out->NormalPower = 2u;
+    out->SigmaDepth = 0.25f;
+    out->SigmaColor = 0.5f;
+    return RT_OK;
+}
+
 extern "C" int rt_trace_last_info(rt_device *d, rt_trace_info *out) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_info: NULL argument");

@@ -335,6 +335,22 @@ extern "C" int rtk_launch_tile_counts_step(void *counts, const void *delta, uint
 // (DEVICE; rt_first_hit, v4 f32, v4 f32; each may be NULL, not all) are arguments of their own: TraceArgs does not grow.
 extern "C" int rtk_launch_first_hit(const TraceArgs *a, int simd, int cull, int centre, void *hit, float *normal,
                                     float *albedo, hipStream_t stream);
+// One pass of rt_denoise (rt_denoise.hip; the filter is defined in rt_trace.h): src -> dst at `step`.
+struct DenoiseArgs {
+    const float *src;     // I_i (pass 0: Mean), v4 f32
+    float *dst;           // I_{i+1}
+    const void *hit;      // rt_first_hit per pixel
+    const float *normal;  // read when normal_power != 0
+    const float *albedo;  // read when demod_in or remod_out
+    uint32_t *rgba8;      // written when non-NULL (the last pass alone names it)
+    uint32_t width, height, step;
+    uint32_t normal_power;   // k: d^(2^k)
+    float sigma_depth, ic;   // 0: that stop is off
+    uint32_t demod_in;       // pass 0 of RT_DENOISE_DEMODULATE: every tap read is Mean / a
+    uint32_t remod_out;      // its last pass: the result is multiplied by the centre's a
+    uint32_t srgb_pow;
+};
+extern "C" int rtk_launch_denoise_pass(const DenoiseArgs *a, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

@@ -243,6 +243,60 @@ int plan_first_hit(bool have_device, bool scene_set, const rt_camera_info *cam, 
     return RT_OK;
 }
 
+int plan_denoise(const rt_denoise_desc *d, DenoisePlan &plan) {
+    if (!d) return rt_fail(RT_EINVAL, "rt_denoise: NULL argument");
+    if (d->Size != sizeof(rt_denoise_desc))
+        return rt_fail(RT_EINVAL, "rt_denoise_desc: Size %u, this library's is %zu", d->Size, sizeof(rt_denoise_desc));
+    if (rt_tile_count(d->Width, d->Height, nullptr) == 0u)
+        return rt_fail(RT_EINVAL, "rt_denoise: bad image size %ux%u", d->Width, d->Height);
+    if (d->Iterations < 1u || d->Iterations > RT_DENOISE_MAX_ITERATIONS)
+        return rt_fail(RT_EINVAL, "rt_denoise: Iterations %u (1..%u)", d->Iterations, RT_DENOISE_MAX_ITERATIONS);
+    if (d->Flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SRGB_POW))
+        return rt_fail(RT_EINVAL, "rt_denoise: unknown flags 0x%x", d->Flags);
+    if (d->NormalPower > 8u) return rt_fail(RT_EINVAL, "rt_denoise: NormalPower %u (0..8)", d->NormalPower);
+    // (a NaN fails the first comparison, an infinity the second)
+    if (!(d->SigmaDepth >= 0.0f && d->SigmaDepth <= 3.402823466e+38f))
+        return rt_fail(RT_EINVAL, "rt_denoise: SigmaDepth is negative, NaN or infinite");
+    if (!(d->SigmaColor >= 0.0f && d->SigmaColor <= 3.402823466e+38f))
+        return rt_fail(RT_EINVAL, "rt_denoise: SigmaColor is negative, NaN or infinite");
+    if (!d->Mean) return rt_fail(RT_EINVAL, "rt_denoise: Mean is NULL");
+    if (!d->Hit) return rt_fail(RT_EINVAL, "rt_denoise: Hit is NULL");
+    if (!d->Out) return rt_fail(RT_EINVAL, "rt_denoise: Out is NULL");
+    if (!d->Normal && d->NormalPower != 0u)
+        return rt_fail(RT_EINVAL, "rt_denoise: Normal is NULL with NormalPower %u", d->NormalPower);
+    if (!d->Albedo && (d->Flags & RT_DENOISE_DEMODULATE))
+        return rt_fail(RT_EINVAL, "rt_denoise: Albedo is NULL with RT_DENOISE_DEMODULATE");
+    if (!d->Scratch && d->Iterations >= 2u)
+        return rt_fail(RT_EINVAL, "rt_denoise: Scratch is NULL with Iterations %u", d->Iterations);
+    const struct {
+        const void *p;
+        uintptr_t mask;
+        const char *name;
+    } planes[] = {{d->Mean, 15u, "Mean"}, {d->Hit, 7u, "Hit"},          {d->Normal, 15u, "Normal"}, {d->Albedo, 15u, "Albedo"},
+                  {d->Out, 15u, "Out"},   {d->Scratch, 15u, "Scratch"}, {d->Rgba8, 3u, "Rgba8"}};
+    for (const auto &pl : planes)
+        if ((uintptr_t)pl.p & pl.mask)
+            return rt_fail(RT_EINVAL, "rt_denoise: %s is not %u-byte aligned", pl.name, (unsigned)pl.mask + 1u);
+    if ((const float *)d->Out == d->Mean)
+        return rt_fail(RT_EINVAL, "rt_denoise: Out is Mean (the filter does not run in place)");
+    // (a Scratch the call never touches is compared all the same: one rule for every Iterations)
+    if (d->Scratch && (const float *)d->Scratch == d->Mean) return rt_fail(RT_EINVAL, "rt_denoise: Scratch is Mean");
+    if (d->Scratch && d->Scratch == d->Out) return rt_fail(RT_EINVAL, "rt_denoise: Scratch is Out");
+    plan = DenoisePlan();
+    plan.n_passes = d->Iterations;
+    plan.ic0 = d->SigmaColor > 0.0f ? 1.0f / d->SigmaColor : 0.0f;
+    const float *src = d->Mean;
+    for (uint32_t i = 0; i < plan.n_passes; ++i) {
+        DenoisePass &p = plan.pass[i];
+        p.src = src;
+        p.dst = ((plan.n_passes - 1u - i) & 1u) ? d->Scratch : d->Out;  // the last pass writes Out
+        p.step = 1u << i;
+        p.ic = plan.ic0 * (float)p.step;
+        src = p.dst;
+    }
+    return RT_OK;
+}
+
 // The key: every word the cull masks, the live list and the learned order depend on.
 static void launch_key(const LaunchPlan &p, const SceneFacts &sf, int rs, const rt_trace_desc &desc,
                        const TileSelection *sel, const TraceArgs &a, std::vector<uint32_t> &key) {

@@ -179,6 +179,23 @@ int plan_first_hit(bool have_device, bool scene_set, const rt_camera_info *cam, 
                    const uint32_t *tiles, uint32_t n_tiles, uint32_t flags, const rt_first_hit_planes *out,
                    std::vector<uint32_t> &bits, FirstHitCall &call);
 
+// rt_denoise without a device: everything the call refuses (the planes' pointers are compared, never followed)
+// and its passes in launch order.  Pass i reads `src` and writes `dst` at step 1 << i with the colour stop's
+// ic = ic0 * (float)step (ic0 = 1.0f / SigmaColor, or 0 without a colour stop); pass 0 reads Mean, every later
+// pass what the one before it wrote, and Scratch and Out alternate so that the last pass writes Out.
+struct DenoisePass {
+    const float *src = nullptr;
+    float *dst = nullptr;
+    uint32_t step = 0;
+    float ic = 0.0f;
+};
+struct DenoisePlan {
+    DenoisePass pass[RT_DENOISE_MAX_ITERATIONS];
+    uint32_t n_passes = 0;
+    float ic0 = 0.0f;
+};
+int plan_denoise(const rt_denoise_desc *desc, DenoisePlan &plan);
+
 // Which table TraceArgs.clusters names.
 enum { kTableNone = 0, kTablePlain, kTableExpanded };
 // The rule set's two cluster tables on the device: opaque to the plan, which only chooses between them.
