@@ -171,7 +171,8 @@ typedef struct rt_device_options {
     int32_t Cull;                /* primary-ray cone cull and dead-tile fold (default on)            */
     int32_t Prefilter;           /* secondary-ray prefilter (default: per scene)                     */
     int32_t PrefilterRelative;   /* per-lane prefilter thresholds (default: per scene)               */
-    int32_t Clusters;            /* cluster walk (default: scenes of <= 128 groups; ON: any size)    */
+    int32_t Clusters;            /* cluster walk (default and ON: scenes of <= 128 groups, the       */
+                                 /* largest a table is built for; beyond, ON is ignored)             */
     int32_t ClusterCount;        /* k-means top clusters K >= 2 (0: ~1.25 sqrt(n) or n / 8..17)      */
     int32_t SubClusterSpheres;   /* spheres per sub-cluster of two-level tables (0: 3, per-lane 4)   */
     int32_t SecondaryThreshold;  /* lanes a secondary round waits for (0: 24/40/48 by walk size)     */

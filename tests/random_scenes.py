@@ -15,7 +15,8 @@ only in one regime, so this generator builds scenes that stress the slack:
 - random materials: diffuse, specular, dielectric (IOR < 1 and > 1), emissive,
   with and without the sky term.
 Scenes are rt_scalar_sphere records (main.cpp:17-21) converted to groups as
-ConvertScalarSpheresToSIMDSpheres does (rt.scene_from_spheres)."""
+ConvertScalarSpheresToSIMDSpheres does (rt.scene_from_spheres).
+Beside the seeds, `named` gives sized and derived inputs for the regimes no seed draws (SIZED, "tiny")."""
 import numpy as np
 
 F = np.float32
@@ -29,20 +30,26 @@ def _camera_pos(look, distance, x_angle, y_height):
     return np.array([np.cos(x_angle) * distance + look[0], y_height + look[1], np.sin(x_angle) * distance + look[2]])
 
 
-def make(seed: int, n_max: int = 1060):
-    """Returns dict(spheres (N,20) f32, use_sky, cameras=[(look_at, distance, x_angle, y_height, kind)])."""
+def make(seed: int, n_max: int = 1060, *, n: int = None, cloud: bool = None):
+    """Returns dict(spheres (N,20) f32, use_sky, cameras=[(look_at, distance, x_angle, y_height, kind)]).
+    n and cloud, where given, replace the seed's own sphere count and its cloud/wide choice: the
+    seed's draws for both are still consumed, so every later stream (positions, adversarial pairs,
+    materials, cameras) is drawn in the same order, and a seed without overrides keeps every byte
+    (tests/golden/random_scene_digests.json)."""
     rng = np.random.default_rng(seed)
     scale = float(10.0 ** rng.uniform(-2, 2))
     # "cloud" scenes (radii within one decade, like the built-in Floating Spheres)
     # keep the scene-wide prefilter bound useful, so the cluster walk and its
     # behind-origin rule run; "wide" scenes (radii over three decades, a huge
     # sphere) take the per-lane thresholds
-    cloud = rng.random() < 0.4
-    if cloud:
-        n = int(rng.integers(8, 257))
+    drawn_cloud = rng.random() < 0.4
+    if drawn_cloud:
+        drawn_n = int(rng.integers(8, 257))
     else:  # mostly small scenes (fast oracle), some large, one in ten at the maximum
-        n = int(rng.choice([rng.integers(1, 9), rng.integers(9, 80), rng.integers(80, 300), n_max],
-                           p=[0.25, 0.45, 0.2, 0.1]))
+        drawn_n = int(rng.choice([rng.integers(1, 9), rng.integers(9, 80), rng.integers(80, 300), n_max],
+                                 p=[0.25, 0.45, 0.2, 0.1]))
+    cloud = drawn_cloud if cloud is None else bool(cloud)
+    n = drawn_n if n is None else int(n)
     extent = scale * rng.uniform(1.0, 4.0)
     c = rng.uniform(-extent, extent, (n, 3))
     r = scale * (10.0 ** rng.uniform(np.log10(0.05), np.log10(0.3), n) if cloud else 10.0 ** rng.uniform(-3, 0, n))
@@ -92,6 +99,45 @@ def make(seed: int, n_max: int = 1060):
     cams.append((centroid, float(extent * rng.uniform(1.5, 3.0)), float(rng.uniform(-6, 6)),
                  float(extent * rng.uniform(-0.3, 0.3)), "grazing"))
     return {"spheres": sp, "use_sky": use_sky, "cameras": cams, "scale": scale, "n": n, "cloud": cloud}
+
+
+# Sized and derived inputs beside the seeds, for the regimes no seed draws (checked on the CPU by
+# tests/test_random_scene_inputs.py, traced by tests/test_gpu_random_scene_kernels.py).  Group counts are
+# those of the bare scene / with the four grazing spheres the GPU tests add.
+SIZED = {
+    "wide400": dict(seed=18, n=400, cloud=False),    # 100 / 101 groups: a two-level per-lane table of four mask words
+    "wide130": dict(seed=18, n=520, cloud=False),    # 130 / 131 groups: the first size past the cluster table's 128
+    "cloud130": dict(seed=6, n=520, cloud=True),
+    "wide165": dict(seed=18, n=660, cloud=False),    # 165 / 166 groups: past the four-wave kernels' LDS image (164)
+    "cloud165": dict(seed=6, n=660, cloud=True),
+    "cloud2w": dict(seed=6, n=200, cloud=True),      # 50 / 51 groups: a scene-wide table of two mask words
+    "cloud4w": dict(seed=6, n=400, cloud=True),      # 100 / 101 groups: a scene-wide table of four mask words
+}
+TINY_SEED, TINY_RADIUS = 34, 2e-6
+NAMED = ("tiny",) + tuple(SIZED)
+SEED_NAMES = tuple(f"seed{s}" for s in range(56))
+# The inputs the forced device options run on: a scene of <= 2 groups (merged rounds), a small wide scene, a wide
+# scene with a huge sphere, a one-level and a two-level cloud, 265 groups, tiny, both 130- and 165-group pairs,
+# and the two four-word tables (each property checked by tests/test_random_scene_inputs.py)
+OPTION_INPUTS = ("seed29", "seed1", "seed16", "seed3", "seed31", "seed18", "tiny", "wide130", "cloud130",
+                 "wide165", "cloud165", "cloud4w", "wide400")
+
+
+def named(name: str):
+    """(spec, seed of its grazing spheres) of an input by name: "seed<k>" is make(k) as it is; a SIZED
+    name is its seed with the sphere count and the cloud/wide choice fixed; "tiny" is seed 34's spheres
+    with the smallest radius set to 2e-6, so that r^2 = 4e-12 lies below 2^-36, the short square
+    root's proven range (the host must clear that flag and route the run-time kernel)."""
+    if name.startswith("seed"):
+        seed = int(name[4:])
+        return make(seed), seed
+    if name == "tiny":
+        spec = make(TINY_SEED)
+        sp = spec["spheres"].copy()
+        sp[int(np.argmin(sp[:, 4])), 4] = F(TINY_RADIUS)
+        spec["spheres"] = sp
+        return spec, TINY_SEED
+    return make(**SIZED[name]), SIZED[name]["seed"]
 
 
 def add_grazing_spheres(rt, spec, W, H, count=4, seed=0):
