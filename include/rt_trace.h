@@ -949,6 +949,15 @@ int rt_scene_direction_members(const rt_scene *scene, uint32_t enable_simd, floa
  * per axis): face = the largest component by magnitude and its sign, the other two components index the
  * face's n x n grid as they are. */
 uint32_t rt_direction_cell(float dx, float dy, float dz);
+/* The union step of that walk, alone (test/inspection hook): one wave of 64 lanes runs the kernels' own union
+ * function with only the lanes of `lanes` enabled (bit l = lane l; 0 is refused: a round has at least one
+ * lane) and returns the OR of their words.  words: one mask per lane, 64 uint32 for mask_bits = 32, or 64
+ * pairs {low, high} for mask_bits = 64; out_union = {low, high} (high = 0 at 32 bits).  The union enables
+ * every lane while it reduces, so each lane, enabled or not, also writes canary_in[l] to a register of its
+ * own before the union and stores it to canary_out[l] after it: canary_out == canary_in shows that the
+ * reduction wrote no register that belongs to a lane outside `lanes`. */
+int rt_direction_union(rt_device *dev, const uint32_t *words, uint32_t mask_bits, uint64_t lanes,
+                       const uint32_t *canary_in, uint32_t out_union[2], uint32_t *canary_out);
 const char *rt_last_error(void);
 
 /* ----------------------------------------------- OnInit / OnRender driver */

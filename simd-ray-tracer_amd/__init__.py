@@ -281,6 +281,7 @@ SIGNATURES = {
                                          POINTER(RtDirectionTableInfo)]),
     "rt_scene_direction_members": (c_int, [POINTER(RtScene), c_uint32, c_void_p, c_uint32, POINTER(c_uint32)]),
     "rt_direction_cell": (c_uint32, [c_float, c_float, c_float]),
+    "rt_direction_union": (c_int, [c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_void_p, c_void_p]),
     "rt_trace_last_direction_table": (c_int, [c_void_p, POINTER(c_uint32)]),
     "rt_last_error": (c_char_p, []),
     "rt_on_init": (c_int, [POINTER(RtInitParams)]),
@@ -728,6 +729,19 @@ class Device:
             _check(lib().rt_trace_last_direction_table(self.handle, ctypes.byref(dt)), "rt_trace_last_direction_table")
         out["DirectionTable"] = int(dt.value)
         return out
+
+    def direction_union(self, words: np.ndarray, lanes: int, canary: np.ndarray):
+        """rt_direction_union: the direction walk's union of 64 lane words (uint32 or uint64) with only the
+        lanes of the bit mask `lanes` enabled -> (the union, the 64 canaries read back)."""
+        words = np.ascontiguousarray(words)
+        assert words.shape == (64,) and words.dtype in (np.uint32, np.uint64), (words.shape, words.dtype)
+        canary = np.ascontiguousarray(canary, np.uint32)
+        assert canary.shape == (64,)
+        u = np.zeros(2, np.uint32)
+        back = np.zeros(64, np.uint32)
+        _check(lib().rt_direction_union(self.handle, words.ctypes.data, 8 * words.dtype.itemsize, int(lanes),
+                                        canary.ctypes.data, u.ctypes.data, back.ctypes.data), "rt_direction_union")
+        return int(u[0]) | (int(u[1]) << 32), back
 
     def reserve(self, width: int, local_rows: int) -> None:
         """rt_device_reserve: pre-size the launch buffers for bands up to width x local_rows."""

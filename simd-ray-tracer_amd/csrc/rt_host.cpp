@@ -1183,6 +1183,36 @@ extern "C" int rt_trace_last_direction_table(rt_device *d, uint32_t *out) {
     return RT_OK;
 }
 
+extern "C" int rt_direction_union(rt_device *d, const uint32_t *words, uint32_t mask_bits, uint64_t lanes,
+                                  const uint32_t *canary_in, uint32_t out_union[2], uint32_t *canary_out) {
+    DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (!d || !words || !canary_in || !out_union || !canary_out)
+        return fail(RT_EINVAL, "rt_direction_union: NULL argument");
+    if (mask_bits != 32u && mask_bits != 64u) return fail(RT_EINVAL, "rt_direction_union: MaskBits %u is not 32 or 64", mask_bits);
+    if (lanes == 0ull) return fail(RT_EINVAL, "rt_direction_union: no lane (a round has at least one)");
+    HIP_OK(hipSetDevice(d->ordinal));
+    const bool wide = mask_bits == 64u;
+    uint32_t h_in[192] = {}, h_out[66] = {};
+    for (uint32_t l = 0; l < 64u; ++l) {
+        h_in[l] = wide ? words[2u * l] : words[l];
+        h_in[64u + l] = wide ? words[2u * l + 1u] : 0u;
+        h_in[128u + l] = canary_in[l];
+    }
+    uint32_t *d_buf = nullptr;
+    if (hipMalloc(&d_buf, sizeof(h_in) + sizeof(h_out)) != hipSuccess) return fail(RT_ENOMEM, "rt_direction_union: device allocation");
+    int rc = RT_OK;
+    if (hipMemcpy(d_buf, h_in, sizeof(h_in), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_buf + 192, 0, sizeof(h_out)) != hipSuccess ||
+        rtk_launch_direction_union(d_buf, lanes, wide ? 1u : 0u, d_buf + 192, nullptr) != 0 ||
+        hipMemcpy(h_out, d_buf + 192, sizeof(h_out), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(RT_EIO, "rt_direction_union: %s", hipGetErrorString(hipGetLastError()));
+    (void)hipFree(d_buf);
+    if (rc != RT_OK) return rc;
+    out_union[0] = h_out[0], out_union[1] = h_out[1];
+    memcpy(canary_out, h_out + 2, 64u * sizeof(uint32_t));
+    return RT_OK;
+}
+
 extern "C" int rt_device_synchronize(rt_device *d) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (!d) return fail(RT_EINVAL, "rt_device_synchronize: NULL device");

@@ -150,7 +150,10 @@ static inline bool rtk_prefilter_expanded(uint32_t prefilter) { return prefilter
 enum { kWalkAny = 0, kWalkGroups, kWalkCl1, kWalkCl2, kWalkCl4, kWalkCl1Rel, kWalkCl2Rel, kWalkCl4Rel,
        // kWalkCl1 with the direction table choosing the member entries (rtk_walk.h direction_groups): a kernel of
        // its own, never a request -- TraceArgs.walk and rt_trace_info.Walk stay kWalkCl1, rtk_walk_kernel picks it
-       kWalkCl1Dir };
+       kWalkCl1Dir,
+       // the same with 64-bit masks (more than 16 groups: rt_layout.h dir_mask64): the mask's width is a fact of
+       // the kernel, so a round tests it nowhere
+       kWalkCl1Dir64 };
 // Compile-time flag of trace_kernel, off in every value above: OR'ed into the kernel's WALK template
 // value it compiles the per-tile counts variant (TraceArgs.tile_counts_at).  A flag bit of an existing
 // parameter rather than a parameter of its own, so that the kernels without it keep their symbols.
@@ -185,6 +188,8 @@ static inline bool rtk_tile_counts_four_wave(uint32_t scene_in_lds, int src) { r
 //                   exists (prefilter == kPrefilterDirection: the expanded table is in use, the host built the
 //                   block -- rt_device_options DirectionTable -- and lays it behind the table), the walk has one
 //                   mask word and the scene at most kDirMaxGroups groups (128 spheres); else kWalkCl1 as before.
+//                   The width of the table's masks (dir_mask64) is a fact too: kWalkCl1Dir holds the 32-bit union
+//                   and walk, kWalkCl1Dir64 the 64-bit ones, chosen here by the function the packer lays the table out by.
 //                   The host offers the block by default to the shapes of at most 8 lanes per pixel
 //                   (rtk_direction_default): the 16-lane shape is the 8-rank band share's, launches of half a
 //                   millisecond, which measured 3.5 % slower with it; DirectionTable on offers it there too.
@@ -216,7 +221,7 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
         return kWalkAny;
     if (a.walk == (uint32_t)kWalkCl1 && a.prefilter == (uint32_t)kPrefilterDirection && a.cl_words == 1u &&
         a.n_groups <= kDirMaxGroups)
-        return kWalkCl1Dir;
+        return dir_mask64(a.n_groups) ? kWalkCl1Dir64 : kWalkCl1Dir;
     // (and the expanded table is read by no other kernel: the host decides with rtk_walk_expanded)
     return a.walk <= (uint32_t)kWalkCl4Rel ? a.walk : (uint32_t)kWalkAny;
 }
@@ -224,13 +229,14 @@ static inline uint32_t rtk_walk_kernel(const TraceArgs &a, int cull, int lanes_p
 // table, prefilter = kPrefilterExpanded), asks this, and puts the plain table back where the answer is no.
 static inline bool rtk_walk_expanded(const TraceArgs &a, int cull, int lanes_per_pixel) {
     const uint32_t k = rtk_walk_kernel(a, cull, lanes_per_pixel);
-    return (k >= (uint32_t)kWalkCl1 && k <= (uint32_t)kWalkCl4) || k == (uint32_t)kWalkCl1Dir;
+    return (k >= (uint32_t)kWalkCl1 && k <= (uint32_t)kWalkCl4) || k == (uint32_t)kWalkCl1Dir || k == (uint32_t)kWalkCl1Dir64;
 }
 // The launch shapes the direction block is offered to without being asked for (rt_plan.cpp route_kernel).
 constexpr bool rtk_direction_default(int lanes_per_pixel) { return lanes_per_pixel <= 8; }
 // Whether it is the direction walk's kernel (rt_trace_last_direction_table).
 static inline bool rtk_walk_direction(const TraceArgs &a, int cull, int lanes_per_pixel) {
-    return rtk_walk_kernel(a, cull, lanes_per_pixel) == (uint32_t)kWalkCl1Dir;
+    const uint32_t k = rtk_walk_kernel(a, cull, lanes_per_pixel);
+    return k == (uint32_t)kWalkCl1Dir || k == (uint32_t)kWalkCl1Dir64;
 }
 
 enum { kStatPriIters = 0, kStatPriLanes, kStatSecIters, kStatSecLanes, kStatPriGroups, kStatSecHitGroups,
@@ -268,6 +274,10 @@ static const uint32_t kMaxLdsGroups = (65536u - 8192u - 2048u) / (16u * kGroupF4
 
 extern "C" int rtk_launch_trace(const TraceArgs *a, int simd, int src, int cull, int lanes_per_pixel,
                                 hipStream_t stream);
+// One wave of the direction walk's union under exec = lanes (rt_direction_union; rt_trace.hip):
+// in = 64 low words, 64 high words, 64 canaries; out = the union's two words, 64 canaries.
+extern "C" int rtk_launch_direction_union(const uint32_t *in, uint64_t lanes, uint32_t wide, uint32_t *out,
+                                          hipStream_t stream);
 // Heaviest-first tile order for the next launch from this launch's costs
 // (resets the costs); n = rtk_tile_count(...) of the launch geometry.
 // scratch: rtk_tile_sort_scratch(n) bytes of device memory

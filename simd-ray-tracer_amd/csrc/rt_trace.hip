@@ -21,6 +21,28 @@ extern "C" int rtk_launch_trace_grid(const TraceArgs *a, int simd, int src, int 
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+// rt_direction_union (inspection hook): one wave runs the direction walk's union (rtk_walk.h wave_or) under
+// exec = lanes.  in: 64 low words, 64 high words, 64 canary words; out: the union's two words, then each
+// lane's canary -- a register every lane, active or not, writes before the union and reads back after it.
+__global__ void __launch_bounds__(64) direction_union_kernel(const uint32_t *in, uint64_t lanes, uint32_t wide, uint32_t *out) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t lo = in[lane], hi = in[64u + lane];
+    uint32_t canary = in[128u + lane];
+    asm volatile("" : "+v"(canary));  // (a VGPR of its own from here on)
+    if ((lanes >> lane) & 1ull) {
+        const uint64_t u = wide ? rtk::wave_or<true>(lo, hi) : rtk::wave_or<false>(lo, 0u);
+        if (lane == (uint32_t)__builtin_ctzll(lanes)) out[0] = (uint32_t)u, out[1] = (uint32_t)(u >> 32);
+    }
+    asm volatile("" : "+v"(canary));
+    out[2u + lane] = canary;
+}
+
+extern "C" int rtk_launch_direction_union(const uint32_t *in, uint64_t lanes, uint32_t wide, uint32_t *out,
+                                          hipStream_t stream) {
+    hipLaunchKernelGGL(direction_union_kernel, dim3(1), dim3(64), 0, stream, in, lanes, wide, out);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 extern "C" int rtk_launch_trace(const TraceArgs *a, int simd, int src, int cull, int lanes_per_pixel,
                                 hipStream_t stream) {
     return rtk_launch_trace_grid(a, simd, src, cull, lanes_per_pixel,

@@ -77,7 +77,9 @@ template <int WALK> struct Walk {
     static constexpr int W = WALK == kWalkCl2 || WALK == kWalkCl2Rel ? 2 : WALK == kWalkCl4 || WALK == kWalkCl4Rel ? 4 : 1;
     static constexpr bool REL = WALK == kWalkCl1Rel || WALK == kWalkCl2Rel || WALK == kWalkCl4Rel;
     static constexpr bool CLUSTERS = WALK >= kWalkCl1;
-    static constexpr bool DIR = WALK == kWalkCl1Dir;  // member entries by the direction table (rtk_walk.h direction_groups)
+    // member entries by the direction table (rtk_walk.h direction_groups); DIR64: its masks are 64 bits wide
+    static constexpr bool DIR = WALK == kWalkCl1Dir || WALK == kWalkCl1Dir64;
+    static constexpr bool DIR64 = WALK == kWalkCl1Dir64;
 };
 
 }  // namespace rtk

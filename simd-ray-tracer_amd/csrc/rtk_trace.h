@@ -718,7 +718,7 @@ void trace_kernel(TraceArgs a) {
                         if (SRC == kSrcSmem && pf && (Walk<WALK>::CLUSTERS || a.n_cpairs)) {
                             PfStats *ps = st.pf_round();
                             if constexpr (Walk<WALK>::DIR) {
-                                direction_groups<SIMD>(a, ray, h, fast, own, dir_row, ps);
+                                direction_groups<SIMD, Walk<WALK>::DIR64>(a, ray, h, fast, own, dir_row, ps);
                             } else if constexpr (Walk<WALK>::CLUSTERS) {
                                 // (the scene-wide walk kernels hold the expanded prefilter: rtk_walk.h pair_prefilter_x)
                                 clustered_groups<SIMD, Walk<WALK>::W, GS, Walk<WALK>::REL, !Walk<WALK>::REL>(a, lds_groups, ray, h, fast,
@@ -908,6 +908,7 @@ static void launch_p(const TraceArgs *a, int simd, int src, int cull, uint32_t n
         case kWalkCl2Rel: RTK_LAUNCH_SOLO(S, true, kWalkCl2Rel); return;      \
         case kWalkCl4Rel: RTK_LAUNCH_SOLO(S, true, kWalkCl4Rel); return;      \
         case kWalkCl1Dir: RTK_LAUNCH_SOLO(S, true, kWalkCl1Dir); return;      \
+        case kWalkCl1Dir64: RTK_LAUNCH_SOLO(S, true, kWalkCl1Dir64); return;  \
         default: break;                                                       \
     }
             if (simd) { RTK_WALKS(true) } else { RTK_WALKS(false) }

@@ -818,11 +818,92 @@ __device__ __forceinline__ bool origin_near(const Sample &p, float4 sc) {
     return __builtin_fabsf(__builtin_fmaf(cc, -kOwnCc, sc.w)) < sc.w * 0x1p-6f;
 }
 
-// The OR of v over the active lanes, in an SGPR: the lowest lane with bits still missing from the union adds
-// its word until none has any (a round's lanes leave about one sphere and share few cells, so a few trips;
-// each lane's own-pair bit is set, so at least one).  trips: the diagnostic build's count.
-__device__ __forceinline__ uint32_t wave_or(uint32_t v, uint32_t &trips) {
-    uint32_t u = 0u;
+// The OR of v over the active lanes, in an SGPR, as a fixed reduction: no loop, no branch.  A round runs under
+// exec = the round's lanes, and a butterfly under partial exec loses words (lanes 0 and 3 alone: lane 0 reads
+// lanes 1 and 2, which computed nothing -- a value cannot pass through an inactive lane).  So the block
+// enables every lane, takes the word as 0 outside the saved exec mask, ORs within each row of 16 lanes by the
+// four DPP controls of trace_kernel's parked_frontier (lane ^ 1, lane ^ 2, the other quad of the half row, the
+// other half of the row), reads one lane per row and puts exec back.  Only t, the block's own register, is
+// written while the inactive lanes are enabled.  Wait states inside the block: a VALU write of t, then a DPP
+// read of t: 2 (s_nop 1); then the lane reads: 1 (s_nop 0).
+// WIDE: both words of a 64-bit mask in the same all-lanes region (the second word's DPP step is one of the
+// first's two wait states).
+template <bool WIDE>
+__device__ __forceinline__ uint64_t wave_or(uint32_t lo, uint32_t hi) {
+    uint64_t keep;
+    uint32_t t, u, r1, r2, r3;
+    if constexpr (!WIDE) {
+        asm volatile(
+            "s_or_saveexec_b64 %[keep], -1\n\t"
+            "v_cndmask_b32_e64 %[t], 0, %[v], %[keep]\n\t"
+            "s_nop 1\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 1\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 1\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 1\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] row_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 0\n\t"
+            "v_readlane_b32 %[u], %[t], 0\n\t"
+            "v_readlane_b32 %[r1], %[t], 16\n\t"
+            "v_readlane_b32 %[r2], %[t], 32\n\t"
+            "v_readlane_b32 %[r3], %[t], 48\n\t"
+            "s_mov_b64 exec, %[keep]\n\t"
+            "s_or_b32 %[u], %[u], %[r1]\n\t"
+            "s_or_b32 %[r2], %[r2], %[r3]\n\t"
+            "s_or_b32 %[u], %[u], %[r2]"
+            : [keep] "=&s"(keep), [t] "=&v"(t), [u] "=&s"(u), [r1] "=&s"(r1), [r2] "=&s"(r2), [r3] "=&s"(r3)
+            : [v] "v"(lo)
+            : "scc");
+        return (uint64_t)u;
+    } else {
+        uint32_t t1, u1, q1, q2, q3;
+        asm volatile(
+            "s_or_saveexec_b64 %[keep], -1\n\t"
+            "v_cndmask_b32_e64 %[t], 0, %[v], %[keep]\n\t"
+            "v_cndmask_b32_e64 %[t1], 0, %[w], %[keep]\n\t"
+            "s_nop 0\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_or_b32_dpp %[t1], %[t1], %[t1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 0\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_or_b32_dpp %[t1], %[t1], %[t1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 0\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "v_or_b32_dpp %[t1], %[t1], %[t1] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 0\n\t"
+            "v_or_b32_dpp %[t], %[t], %[t] row_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "v_or_b32_dpp %[t1], %[t1], %[t1] row_mirror row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 0\n\t"
+            "v_readlane_b32 %[u], %[t], 0\n\t"
+            "v_readlane_b32 %[r1], %[t], 16\n\t"
+            "v_readlane_b32 %[r2], %[t], 32\n\t"
+            "v_readlane_b32 %[r3], %[t], 48\n\t"
+            "v_readlane_b32 %[u1], %[t1], 0\n\t"
+            "v_readlane_b32 %[q1], %[t1], 16\n\t"
+            "v_readlane_b32 %[q2], %[t1], 32\n\t"
+            "v_readlane_b32 %[q3], %[t1], 48\n\t"
+            "s_mov_b64 exec, %[keep]\n\t"
+            "s_or_b32 %[u], %[u], %[r1]\n\t"
+            "s_or_b32 %[r2], %[r2], %[r3]\n\t"
+            "s_or_b32 %[u], %[u], %[r2]\n\t"
+            "s_or_b32 %[u1], %[u1], %[q1]\n\t"
+            "s_or_b32 %[q2], %[q2], %[q3]\n\t"
+            "s_or_b32 %[u1], %[u1], %[q2]"
+            : [keep] "=&s"(keep), [t] "=&v"(t), [t1] "=&v"(t1), [u] "=&s"(u), [r1] "=&s"(r1), [r2] "=&s"(r2),
+              [r3] "=&s"(r3), [u1] "=&s"(u1), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3)
+            : [v] "v"(lo), [w] "v"(hi)
+            : "scc");
+        return (uint64_t)u | ((uint64_t)u1 << 32);
+    }
+}
+
+// The diagnostic build's count alone (RTK_STATS lane_pairs): the trips of the union loop wave_or replaced, in
+// which the lowest lane with bits still missing from the union added its word until none had any.  The walk
+// itself runs on wave_or's word.
+__device__ __forceinline__ uint32_t wave_or_trips(uint32_t v) {
+    uint32_t u = 0u, trips = 0u;
     for (;;) {
         const uint64_t b = __builtin_amdgcn_ballot_w64(v != 0u);
         if (b == 0ull) break;
@@ -830,49 +911,27 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v, uint32_t &trips) {
         v &= ~u;
         trips += 1u;
     }
-    return u;
+    return trips;
 }
 
-// ps (RTK_STATS): groups += member entries tested, near_entries as in member_pairs, pairs += sphere pairs
-// rechecked exactly, lane_pairs += trips of the union loop; no cluster entry is tested, and the two cluster
-// counters count the origin measurement instead: cl_top_entered += rounds with a lane that asks for every pair,
-// cl_tested += such lanes.
-template <bool SIMD>
-__device__ __forceinline__ void direction_groups(const TraceArgs &a, const RayPk &ray, Hit &h, bool fast, uint32_t own,
-                                                 uint32_t row, PfStats *ps) {
-    const v4f_t c0 = *(cv4f_t *)a.clusters;
-    const uint32_t at = __float_as_uint(c0.w);  // the block's offset in rows (rt_layout.h)
-    cv4f_t *members = (cv4f_t *)a.clusters + at;
-    const uint32_t n_pairs = 2u * a.n_groups;
-    const uint64_t every = n_pairs >= 64u ? ~0ull : (1ull << n_pairs) - 1ull;  // the pairs there are entries for
-    // the lane's mask: row < 4 n_groups (a sphere the lane has hit) and cell < kDirCells (dir_cell clamps)
-    const bool near = row != kOwnNone;
-    // (the clamp costs one instruction and keeps the gather inside the table whatever a lane carries)
-    const uint32_t idx = (near ? min(row, 4u * a.n_groups - 1u) : 0u) * kDirCells + dir_cell(ray.x.y, ray.y.y, ray.z.y);
-    const uint32_t *rows = (const uint32_t *)(a.clusters + at + dir_member_f4(a.n_groups));
-    uint32_t lo, hi = 0u, trips = 0u;
-    const bool wide = dir_mask64(a.n_groups);  // (wave-uniform)
-    if (wide) {
-        const uint2 m = ((const uint2 *)rows)[idx];
-        lo = m.x;
-        hi = m.y;
-    } else {
-        lo = rows[idx];
-    }
-    if (!near) lo = (uint32_t)every, hi = (uint32_t)(every >> 32);
-    const RayX rx = ray_expand(ray, c0);
-    uint64_t todo = wave_or(lo, trips);
-    if (wide) todo |= (uint64_t)wave_or(hi, trips) << 32;
-    if (ps) {
-        const uint64_t far = __builtin_amdgcn_ballot_w64(!near);
-        ps->lane_pairs += trips, ps->groups += (uint32_t)__builtin_popcountll(todo);
-        ps->cl_top_entered += far != 0ull ? 1u : 0u, ps->cl_tested += (uint32_t)__builtin_popcountll(far);
-    }
+// The member entries of the union `todo`, in pair order (member_pairs<1, false, true>'s body on each): the pairs
+// some lane of the round may accept, as the wave mask of clustered_groups' recheck.  M: the mask's own width,
+// uint32_t up to 32 pairs -- a 32-bit find, one bit cleared and a 32-bit test per entry -- else uint64_t.
+// todo != 0 (every lane's own-pair bit is set): the loop is entered without a test.
+template <typename M>
+__device__ __forceinline__ uint64_t direction_members(cv4f_t *members, const RayX &rx, uint32_t own, M todo, PfStats *ps) {
     uint64_t wave = 0ull;
-    while (todo) {
-        const uint32_t pr = (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
-        // (member_pairs<1, false, true>'s body on entry pr)
+    __builtin_assume(todo != 0);
+    do {
+        uint32_t pr;
+        if constexpr (sizeof(M) == 4) {
+            pr = (uint32_t)__builtin_ctz(todo);
+            // (todo &= ~(1u << pr) compiles to a shift and an and-not)
+            asm("s_bitset0_b32 %0, %1" : "+s"(todo) : "s"(pr));
+        } else {
+            pr = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1ull;
+        }
         const Rows4 er = load_rows4(cl_entry(members, pr * (16u * cl_entry_f4(1u))));
         const v4f_t r0 = er.r0, r1 = er.r1, r2 = er.r2, r3 = er.r3;
         f2 T;
@@ -885,7 +944,59 @@ __device__ __forceinline__ void direction_groups(const TraceArgs &a, const RayPk
         merge_word1(wave, n0m, __builtin_amdgcn_ballot_w64(!(T.x < r3.x)),
                     __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.z)), w0, n1m,
                     __builtin_amdgcn_ballot_w64(!(T.y < r3.y)), __builtin_amdgcn_ballot_w64(own != __float_as_uint(r3.w)), w1);
+    } while (todo != 0);
+    return wave;
+}
+
+// The union of the round's lanes' masks and the member entries of it.  WIDE: 64-bit masks (more than 16 groups).
+template <bool WIDE>
+__device__ __forceinline__ uint64_t direction_union_walk(const TraceArgs &a, cv4f_t *members, const uint32_t *rows,
+                                                         uint32_t idx, bool near, const RayX &rx, uint32_t own, PfStats *ps) {
+    uint32_t lo, hi = 0u;
+    if constexpr (WIDE) {
+        const uint2 m = ((const uint2 *)rows)[idx];
+        lo = m.x;
+        hi = m.y;
+        if (!near) {  // every pair there is an entry for
+            const uint32_t n_pairs = 2u * a.n_groups;
+            const uint64_t every = n_pairs >= 64u ? ~0ull : (1ull << n_pairs) - 1ull;
+            lo = (uint32_t)every, hi = (uint32_t)(every >> 32);
+        }
+    } else {
+        lo = rows[idx];
+        if (!near) lo = 0xFFFFFFFFu >> (32u - 2u * a.n_groups);  // (1 <= n_groups <= 16)
     }
+    const uint64_t todo = wave_or<WIDE>(lo, hi);
+    if (ps) {
+        const uint64_t far = __builtin_amdgcn_ballot_w64(!near);
+        ps->lane_pairs += wave_or_trips(lo) + (WIDE ? wave_or_trips(hi) : 0u);
+        ps->groups += (uint32_t)__builtin_popcountll(todo);
+        ps->cl_top_entered += far != 0ull ? 1u : 0u, ps->cl_tested += (uint32_t)__builtin_popcountll(far);
+    }
+    if constexpr (WIDE) return direction_members<uint64_t>(members, rx, own, todo, ps);
+    else return direction_members<uint32_t>(members, rx, own, (uint32_t)todo, ps);
+}
+
+// ps (RTK_STATS): groups += member entries tested, near_entries as in member_pairs, pairs += sphere pairs
+// rechecked exactly, lane_pairs += trips of the union loop (wave_or_trips); no cluster entry is tested, and the
+// two cluster counters count the origin measurement instead: cl_top_entered += rounds with a lane that asks for
+// every pair, cl_tested += such lanes.
+// WIDE: the table's masks are 64 bits wide (dir_mask64(a.n_groups): the host routes by it, rtk_walk_kernel).
+template <bool SIMD, bool WIDE>
+__device__ __forceinline__ void direction_groups(const TraceArgs &a, const RayPk &ray, Hit &h, bool fast, uint32_t own,
+                                                 uint32_t row, PfStats *ps) {
+    const v4f_t c0 = *(cv4f_t *)a.clusters;
+    const uint32_t at = __float_as_uint(c0.w);  // the block's offset in rows (rt_layout.h)
+    cv4f_t *members = (cv4f_t *)a.clusters + at;
+    // the lane's mask: row < 4 n_groups (a sphere the lane has hit) and cell < kDirCells (dir_cell clamps)
+    const bool near = row != kOwnNone;
+    // (the clamp costs one instruction and keeps the gather inside the table whatever a lane carries)
+    const uint32_t idx = (near ? min(row, 4u * a.n_groups - 1u) : 0u) * kDirCells + dir_cell(ray.x.y, ray.y.y, ray.z.y);
+    const uint32_t *rows = (const uint32_t *)(a.clusters + at + dir_member_f4(a.n_groups));
+    const RayX rx = ray_expand(ray, c0);
+    // (the mask's width is a fact of the kernel -- rt_kernel.h kWalkCl1Dir / kWalkCl1Dir64 -- so a round tests it
+    // nowhere: as a run-time choice it was structurised into mask form around the gather and the walk)
+    uint64_t wave = direction_union_walk<WIDE>(a, members, rows, idx, near, rx, own, ps);
     // (clustered_groups' recheck of a one-word mask)
     cv4f_t *gp = (cv4f_t *)a.groups;
     while (wave) {
