@@ -52,10 +52,13 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return (px + py) + pz;
 }
 
-// Short correctly rounded sequences (each checked against the compiler's
-// IEEE sequence by scripts/mathcheck.hip on gfx950: rcp_rn and sqrt_rn
-// exhaustively over every f32 in [2^-40, 2^40] / [2^-60, 2^60], div_rn on
-// 8.6e9 random and edge-case pairs; all bit-identical).
+// Short correctly rounded sequences.  tests/test_gpu_math_layer.py runs each of
+// them, from this header, alone on the GPU (tests/math_probe) and holds it to the
+// f64 result rounded once: rcp_rn and sqrt_rn on every mantissa of a binade or
+// two and on 4,096 mantissas of every binade of their ranges, div_rn on 3.6e6
+// edge-case and random pairs.  (When they were written, copies of them were
+// compared with the compiler's IEEE sequence over every f32 of [2^-40, 2^40] /
+// [2^-60, 2^60] and on 8.6e9 pairs: DESIGN.md, "Short exact sequences".)
 // RN(1/b) for b in [2^-40, 2^40]: v_rcp_f32 (< 1 ulp) + one Newton step.
 __device__ __forceinline__ float rcp_rn(float b) {
     const float y0 = __builtin_amdgcn_rcpf(b);
@@ -64,9 +67,18 @@ __device__ __forceinline__ float rcp_rn(float b) {
 
 // RN(sqrt(x)) for x = 0 or x in [2^-60, 2^60] (Markstein): y = v_rsq_f32(x),
 // g = RN(x y), h = y / 2, r = x - g^2 (one fma, exact), result RN(g + r h).
-// scripts/mathcheck.hip finds it bit-identical to the IEEE sqrt on every f32 of
-// the range (mode 6, profiles/r06q_mathcheck.txt).  x = 0: v_rsq gives +inf,
-// clamped to 2^64 so g = 0 and the result is +0 (the range's y is below 2^30).
+// Held to the f64 sqrt rounded once by tests/test_gpu_math_layer.py, also from
+// 2^-102 to the top of f32 (beyond what any caller needs: normalize takes len
+// from the IEEE sqrt above 2^40).  x = +0: v_rsq gives +inf, clamped to 2^64 so
+// g = 0 and the result is +0 (the range's y is below 2^30).
+// Outside the domain it is NOT the IEEE sqrt: x < 0 gives -inf or a large
+// negative value (v_rsq is NaN, the clamp's fminf turns it into 2^64; measured
+// -inf on all of [-2^-10, -2^-25]), -inf gives -inf, and -0, +inf and NaN give
+// NaN (-0: -inf * -0; +inf: v_rsq is +0, inf * 0).  The callers: normalize's x is
+// a sum of squares, never negative or -0, and it sends a NaN len (x = +inf) to
+// its IEEE path; linear_to_srgb's is in [0.0031308, 1] or NaN, and NaN stays NaN;
+// shade's two uses are commented there; the candidate root (rtk_walk.h) is
+// guarded by the host's proof (fast_sqrt).
 // Five full-rate ops besides the transcendental, against eight for v_sqrt_f32
 // and its two +-1 ulp residual tests (round 5's form): C2 +2.5 %, RTWeekend
 // +2.3 % (profiles/r06q_sqrt_ab.txt).
@@ -98,8 +110,11 @@ __device__ __forceinline__ float2 fold_weights(uint32_t pc) {
 
 // v3::Normalize (x64_math.h:234-245): IEEE divide by the correctly rounded
 // sqrt, zero when len^2 <= 1e-4.  Fast path: one reciprocal shared by the
-// three quotients; lanes outside its proven range (a quotient below 2^-99
-// or len above 2^40) take the compiler's IEEE sequence.  (The reciprocal from
+// three quotients; lanes outside its proven range (a quotient below 2^-99,
+// or len not a finite value up to 2^40: the test is !(len <= 2^40), so that the
+// NaN sqrt_rn returns for len^2 = +inf, finite components from about 2^63.5,
+// goes there too) take the compiler's IEEE sequence, square root included: the
+// reference's len = +inf then gives quotients of +-0.  (The reciprocal from
 // sqrt_rn's own v_rsq by a Newton step measured equal and was not kept:
 // profiles/r06u_norm_rcp_and_c2_options_ab.txt.)
 __device__ __forceinline__ void normalize(float &x, float &y, float &z) {
@@ -110,10 +125,11 @@ __device__ __forceinline__ void normalize(float &x, float &y, float &z) {
     float qx = div_rn(x, len, inv), qy = div_rn(y, len, inv), qz = div_rn(z, len, inv);
     // (a zero component also takes the IEEE path: rare, and exact either way)
     const float m = __builtin_fminf(__builtin_fminf(__builtin_fabsf(qx), __builtin_fabsf(qy)), __builtin_fabsf(qz));
-    if (__builtin_expect(keep && (m < 0x1p-99f || len > 0x1p40f), 0)) {
-        qx = x / len;
-        qy = y / len;
-        qz = z / len;
+    if (__builtin_expect(keep && (m < 0x1p-99f || !(len <= 0x1p40f)), 0)) {
+        const float ieee_len = __builtin_sqrtf(l2);
+        qx = x / ieee_len;
+        qy = y / ieee_len;
+        qz = z / ieee_len;
     }
     x = keep ? qx : 0.0f;
     y = keep ? qy : 0.0f;
@@ -301,7 +317,10 @@ __device__ __forceinline__ void shade(const Lut &lut, float4 col_spec, float4 em
         const float eta = inside ? ior : dq.x;
         const float dd = dot3(-p.rx.y, -p.ry.y, -p.rz.y, nx, ny, nz);
         const float cos_t = dd < 1.0f ? dd : 1.0f;  // _mm_min_ss
-        // 1 - c*c and |1 - q.q| are 0 or >= 2^-25 (or NaN): inside sqrt_rn's range
+        // |1 - q.q| is +0, >= 2^-25 or NaN: inside sqrt_rn's range (NaN stays NaN).  1 - c*c is +0 or
+        // >= 2^-25 for |c| <= 1; cos_t a few ulps below -1 makes it negative, where the reference's sqrtss
+        // gives NaN and sqrt_rn -inf (or a large negative value): `eta * sin_t > 1` is false for both, and
+        // sin_t has no other use (tests/test_gpu_math_layer.py, test_sqrt_rn_below_zero...)
         const float sin_t = sqrt_rn(1.0f - cos_t * cos_t);
         const bool cant = eta * sin_t > 1.0f;
         const float qx = eta * (p.rx.y + cos_t * nx);
