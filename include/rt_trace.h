@@ -617,6 +617,87 @@ int rt_denoise(const rt_denoise_desc *desc, void *stream);
  * against their 1024-spp means (DESIGN.md has the table).  RT_EINVAL for NULL. */
 int rt_denoise_defaults(rt_denoise_desc *out);
 
+/* ------------------------------------------------- the running mean across a camera move */
+
+#define RT_REPROJECT_SRGB_POW 2u   /* Rgba8 through the exact-pow branch, as RT_FLAG_SRGB_POW */
+
+typedef struct rt_reproject_desc {
+    uint32_t Size;                 /* sizeof(rt_reproject_desc)                                       */
+    uint32_t Width, Height;        /* rt_tile_count(Width, Height) != 0                               */
+    uint32_t Frames;               /* >= 1: frames folded into Mean (traced from PreviousRayCount 0)   */
+    uint32_t MaxHistory;           /* >= Frames: cap of a pixel's history length                      */
+    uint32_t Flags;                /* RT_REPROJECT_SRGB_POW or 0                                      */
+    float    DepthTolerance;       /* 0: no depth test; else relative to the distance; finite, > 0    */
+    const rt_camera_info *Camera;          /* HOST: the camera of Mean and Hit                        */
+    const rt_camera_info *PreviousCamera;  /* HOST: the camera of the history planes                  */
+    const float        *Mean;      /* DEVICE v4 f32, Width*Height, 16-byte aligned: the fresh mean    */
+    const rt_first_hit *Hit;       /* DEVICE, 8-byte aligned: rt_trace_first_hit, RT_HIT_PIXEL_CENTRE, at Camera */
+    const float        *History;       /* DEVICE v4 f32: the previous call's Out      | all three NULL: */
+    const rt_first_hit *HistoryHit;    /* DEVICE: the previous call's Hit             | no history, a   */
+    const uint32_t     *HistoryCount;  /* DEVICE u32, 4-byte aligned: its OutCount    | loop's first frame */
+    float              *Out;       /* DEVICE v4 f32, required                                         */
+    uint32_t           *OutCount;  /* DEVICE u32, required: frames behind each pixel of Out           */
+    uint32_t           *Rgba8;     /* DEVICE or NULL: ColorFromV4(LinearToSRGB(Out))                  */
+} rt_reproject_desc;
+
+/* Carries an accumulated frame across a camera move.  New; the reference's OnRender drops its running mean on
+ * every move (main.cpp:791-806).  For each pixel of the new frame the pass finds where the surface point the
+ * pixel sees lay in the previous frame, gathers the accumulated colour there from the pixels that saw the same
+ * sphere at a consistent distance, and folds the fresh mean into it; a pixel with no such history starts again
+ * from the fresh mean.  A miss never takes history, and what a mirror shows does not follow its surface:
+ * MaxHistory bounds how long either error can live.  Like rt_denoise the pass needs no rt_device, keeps no state,
+ * allocates nothing and does not wait on the host: one kernel launch on `stream` (NULL: the null stream) of the
+ * current HIP device.  The cameras are HOST structs as rt_camera_setup makes them, consumed before the call
+ * returns; only CameraPosition, CameraX, CameraY, FilmCenter, FilmW and FilmH are read, and CameraX and CameraY
+ * are taken to be unit vectors orthogonal to FilmCenter - CameraPosition.  The inputs are only read; no byte
+ * outside Out, OutCount and Rgba8 (when given) is written.  The loop: rt_trace at PreviousRayCount 0 into Mean,
+ * rt_trace_first_hit with RT_HIT_PIXEL_CENTRE into Hit, rt_reproject, optionally rt_denoise of Out for display, then
+ * Out, Hit, OutCount become History, HistoryHit, HistoryCount and the camera PreviousCamera.
+ *
+ * The result is defined operation by operation; every operation is one IEEE f32 operation (no contraction, IEEE
+ * division and square root, denormals kept), so it is one set of bits (tests/reproject_ref.py restates it in numpy):
+ *    dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  primes mark PreviousCamera's fields.
+ *  - Host, once: fv.c = FilmCenter'.c - CameraPosition'.c; ff = dot3(fv, fv); Wf = (float)Width, Hf = (float)Height;
+ *    hw = Wf * 0.5f, hh = Hf * 0.5f.
+ *  - Pixel p = (x, y): kp = Hit[p].Key, tp = Hit[p].T.
+ *  1 Fresh: with History == NULL or kp == RT_HIT_MISS the pixel is fresh: Out.ch = Mean.ch, OutCount = Frames.
+ *  2 Direction, the pixel-centre primary ray of rt_trace_first_hit: fx = -1.0f + ((float)x * 2.0f) / Wf, fy
+ *    likewise; kx = (fx * FilmW) * 0.5f, ky = (fy * FilmH) * 0.5f; P.c = (FilmCenter.c + kx * CameraX.c) + ky *
+ *    CameraY.c; D = Normalize(P - CameraPosition), the reference's Normalize (x64_math.h:234-245): v.c /
+ *    sqrtf(dot3(v, v)), the zero vector where dot3(v, v) <= 1e-4f.
+ *  3 Point: X.c = CameraPosition.c + D.c * tp; V.c = X.c - CameraPosition'.c.
+ *  4 Projection: u = dot3(V, CameraX'), v = dot3(V, CameraY'), d = dot3(V, fv); qx = (u / d) * ff;
+ *    sx = (((qx * 2.0f) / FilmW') + 1.0f) * hw; sy likewise from v, FilmH' and hh (a pixel's centre sits at its
+ *    integer coordinate: the reference's jitter is in [-0.5, 0.5)).  te = sqrtf(dot3(V, V)), lim = DepthTolerance * te.
+ *  5 Range: the pixel is fresh unless d > 0 && sx >= -1.0f && sx < Wf && sy >= -1.0f && sy < Hf (a NaN fails).
+ *    x0 = floorf(sx), ax = sx - x0; y0 = floorf(sy), ay = sy - y0.
+ *  6 Taps q = (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), in that order, w = wx * wy with wx = 1.0f - ax
+ *    at x0 and ax at x0 + 1, wy alike.  acc = (+0, +0, +0), ws = +0, n = 0xFFFFFFFF.  A tap is skipped when it is
+ *    outside the image; when w is not > 0; when HistoryCount[q] == 0; when HistoryHit[q].Key != kp (the whole word,
+ *    RT_HIT_INSIDE included); when a channel of History[q].xyz is not finite (a NaN would live in the history for
+ *    ever); and, with DepthTolerance > 0, when !(fabsf(te - HistoryHit[q].T) <= lim) (the far side of the same
+ *    sphere).  A tap that is kept: acc.ch = acc.ch + w * History[q].ch, ws = ws + w, n = min(n, HistoryCount[q]).
+ *  7 Fold: no tap kept: the pixel is fresh.  Else n = min(n, MaxHistory), H.ch = acc.ch / ws, a = (float)Frames /
+ *    ((float)n + (float)Frames), Out.ch = H.ch + (Mean.ch - H.ch) * a, OutCount = min(n + Frames, MaxHistory) (the
+ *    sum formed without wrapping).
+ *  8 Out.w = Mean[p].w; Rgba8[p], when given, is the RGBA8 of Out.xyz as rt_trace and rt_encode_rgba8 encode it
+ *    (RT_REPROJECT_SRGB_POW: the exact-pow branch).
+ *
+ * RT_EINVAL, with an rt_last_error text and before anything is enqueued: a NULL desc or a wrong Size; a size for
+ * which rt_tile_count is 0; Frames == 0 or MaxHistory < Frames; an unknown flag bit; a DepthTolerance that is
+ * negative, NaN or infinite; a NULL Camera, PreviousCamera, Mean, Hit, Out or OutCount; History, HistoryHit and
+ * HistoryCount not all NULL or all non-NULL; a misaligned plane (Mean, History, Out 16 bytes, Hit, HistoryHit 8,
+ * HistoryCount, OutCount, Rgba8 4); Out equal to Mean or History, OutCount equal to HistoryCount (the pass gathers
+ * from its neighbours: it does not run in place). */
+int rt_reproject(const rt_reproject_desc *desc, void *stream);
+/* Fills *out with Size, Width = Height = 0, Frames = 1, Flags = 0, every pointer NULL and the library's defaults:
+ * MaxHistory = 8 (the built-in scenes are mirrors and glass: over a long orbit a longer history carries more stale
+ * reflection than it removes noise) and DepthTolerance = 0.1f (within 0.001 of no depth test on the three scenes'
+ * mean, and still a guard against the far side of a sphere).  Chosen on the CPU restatement over orbit steps of
+ * 1/16 rad at 1 fresh spp on the three built-in scenes against 256-frame means (DESIGN.md has the tables).
+ * RT_EINVAL for NULL. */
+int rt_reproject_defaults(rt_reproject_desc *out);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call

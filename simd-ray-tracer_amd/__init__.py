@@ -147,6 +147,17 @@ class RtDenoiseDesc(ctypes.Structure):  # rt_denoise_desc: one rt_denoise call, 
 DENOISE_DEMODULATE, DENOISE_SRGB_POW, DENOISE_MAX_ITERATIONS = 1, 2, 8
 
 
+class RtReprojectDesc(ctypes.Structure):  # rt_reproject_desc: one rt_reproject call, 112 B
+    _fields_ = [("Size", c_uint32), ("Width", c_uint32), ("Height", c_uint32), ("Frames", c_uint32),
+                ("MaxHistory", c_uint32), ("Flags", c_uint32), ("DepthTolerance", c_float),
+                ("Camera", POINTER(RtCameraInfo)), ("PreviousCamera", POINTER(RtCameraInfo)), ("Mean", c_void_p),
+                ("Hit", c_void_p), ("History", c_void_p), ("HistoryHit", c_void_p), ("HistoryCount", c_void_p),
+                ("Out", c_void_p), ("OutCount", c_void_p), ("Rgba8", c_void_p)]
+
+
+REPROJECT_SRGB_POW = 2
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -240,6 +251,8 @@ SIGNATURES = {
                                    POINTER(RtFirstHitPlanes), c_void_p]),
     "rt_denoise": (c_int, [POINTER(RtDenoiseDesc), c_void_p]),
     "rt_denoise_defaults": (c_int, [POINTER(RtDenoiseDesc)]),
+    "rt_reproject": (c_int, [POINTER(RtReprojectDesc), c_void_p]),
+    "rt_reproject_defaults": (c_int, [POINTER(RtReprojectDesc)]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -986,6 +999,49 @@ def denoise(width: int, height: int, mean_ptr: int, hit_ptr: int, out_ptr: int, 
                       mean_ptr or None, hit_ptr or None, normal_ptr or None, albedo_ptr or None, out_ptr or None,
                       scratch_ptr or None, rgba8_ptr or None)
     _check(lib().rt_denoise(ctypes.byref(d), c_void_p(stream or 0)), "rt_denoise")
+
+
+def reproject_defaults() -> dict:
+    """rt_reproject_defaults: the library's Frames, MaxHistory and DepthTolerance."""
+    d = RtReprojectDesc()
+    _check(lib().rt_reproject_defaults(ctypes.byref(d)), "rt_reproject_defaults")
+    assert d.Size == ctypes.sizeof(RtReprojectDesc)
+    return dict(frames=d.Frames, max_history=d.MaxHistory, depth_tolerance=d.DepthTolerance)
+
+
+def reproject(width: int, height: int, camera: RtCameraInfo, previous_camera: RtCameraInfo, mean_ptr: int, hit_ptr: int,
+              out_ptr: int, out_count_ptr: int, history_ptr: int = 0, history_hit_ptr: int = 0,
+              history_count_ptr: int = 0, rgba8_ptr: int = 0, frames: int = 1, max_history: Optional[int] = None,
+              depth_tolerance: Optional[float] = None, srgb_pow: bool = False, stream: Optional[int] = None) -> None:
+    """rt_reproject: carries the accumulated frame `history_ptr` (width * height v4 f32, with its first-hit plane
+    `history_hit_ptr` and its per-pixel frame counts `history_count_ptr`, all seen from `previous_camera`) to
+    `camera` and folds the fresh mean `mean_ptr` of `frames` frames into it, guided by Device.trace_first_hit's
+    centre=True plane `hit_ptr` at `camera`: the result into `out_ptr`, its frame counts into `out_count_ptr` (u32)
+    and, when non-zero, its RGBA8 into `rgba8_ptr`.  The three history pointers are 0 together on a loop's first
+    frame.  max_history, depth_tolerance: None takes the library's default (reproject_defaults()); a
+    depth_tolerance of 0 turns the depth test off.  Enqueued on `stream`; needs no Device.  ValueError for a count
+    or a tolerance no call can take, RtError for what the library refuses."""
+    dflt = reproject_defaults()
+    cap = dflt["max_history"] if max_history is None else max_history
+    tol = dflt["depth_tolerance"] if depth_tolerance is None else depth_tolerance
+    for name, v in (("frames", frames), ("max_history", cap)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"reproject: {name} must be an integer in 1..2^32-1, got {v!r}")
+    if int(cap) < int(frames):
+        raise ValueError(f"reproject: max_history {cap!r} is below frames {frames!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not 0.0 <= float(tol) < float("inf"):
+        raise ValueError(f"reproject: depth_tolerance must be a finite number >= 0, got {tol!r}")
+    if float(tol) > float(np.finfo(np.float32).max):
+        raise ValueError(f"reproject: depth_tolerance {tol!r} is not a finite f32")
+    for name, c in (("camera", camera), ("previous_camera", previous_camera)):
+        if not isinstance(c, RtCameraInfo):
+            raise ValueError(f"reproject: {name} must be an RtCameraInfo (camera_setup), got {type(c).__name__}")
+    d = RtReprojectDesc(ctypes.sizeof(RtReprojectDesc), width, height, int(frames), int(cap),
+                        REPROJECT_SRGB_POW if srgb_pow else 0, float(tol), ctypes.pointer(camera),
+                        ctypes.pointer(previous_camera), mean_ptr or None, hit_ptr or None, history_ptr or None,
+                        history_hit_ptr or None, history_count_ptr or None, out_ptr or None, out_count_ptr or None,
+                        rgba8_ptr or None)
+    _check(lib().rt_reproject(ctypes.byref(d), c_void_p(stream or 0)), "rt_reproject")
 
 
 # ------------------------------------------------- OnInit / OnRender mirror

@@ -1152,6 +1152,26 @@ extern "C" int rt_denoise_defaults(rt_denoise_desc *out) {
     return RT_OK;
 }
 
+// The running mean across a camera move (rt_reproject.hip): the refusals and the launch's arguments are the
+// plan's (rt_plan.cpp), the call is one launch.  No device handle, no state, no allocation, no wait.
+extern "C" int rt_reproject(const rt_reproject_desc *desc, void *stream) {
+    ReprojectArgs a;
+    if (const int rc = plan_reproject(desc, a)) return rc;
+    if (rtk_launch_reproject(&a, (hipStream_t)stream) != 0)
+        return fail(RT_EIO, "rt_reproject: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+extern "C" int rt_reproject_defaults(rt_reproject_desc *out) {
+    if (!out) return fail(RT_EINVAL, "rt_reproject_defaults: NULL argument");
+    memset(out, 0, sizeof(*out));
+    out->Size = (uint32_t)sizeof(*out);
+    out->Frames = 1u;
+    out->MaxHistory = 8u;
+    out->DepthTolerance = 0.1f;
+    return RT_OK;
+}
+
 extern "C" int rt_trace_last_info(rt_device *d, rt_trace_info *out) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_info: NULL argument");

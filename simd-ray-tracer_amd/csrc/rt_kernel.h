@@ -361,6 +361,26 @@ struct DenoiseArgs {
     uint32_t srgb_pow;
 };
 extern "C" int rtk_launch_denoise_pass(const DenoiseArgs *a, hipStream_t stream);
+// rt_reproject (rt_reproject.hip; the pass is defined in rt_trace.h): one launch, one thread per pixel.  Both
+// cameras and the host's constants (rt_plan.cpp plan_reproject) travel by value.
+struct ReprojectArgs {
+    const float *mean;            // v4 f32, the fresh mean
+    const void *hit;              // rt_first_hit per pixel, at the new camera
+    const float *history;         // v4 f32, or NULL: no history (history_hit and history_count are NULL with it)
+    const void *history_hit;      // rt_first_hit per pixel, at the previous camera
+    const uint32_t *history_count;
+    float *out;
+    uint32_t *out_count;
+    uint32_t *rgba8;              // written when non-NULL
+    uint32_t width, height, frames, max_history;
+    float depth_tolerance;        // 0: no depth test
+    uint32_t srgb_pow;
+    float cam_pos[3], cam_x[3], cam_y[3], film_center[3], film_w, film_h;  // the new camera
+    float prev_pos[3], prev_x[3], prev_y[3], prev_film_w, prev_film_h;     // the previous camera
+    float fv[3], ff;              // FilmCenter' - CameraPosition' and its squared length
+    float wf, hf, hw, hh;         // (f32)Width, (f32)Height and their halves
+};
+extern "C" int rtk_launch_reproject(const ReprojectArgs *a, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

@@ -297,6 +297,97 @@ int plan_denoise(const rt_denoise_desc *d, DenoisePlan &plan) {
     return RT_OK;
 }
 
+int plan_reproject(const rt_reproject_desc *d, ReprojectArgs &args) {
+    if (!d) return rt_fail(RT_EINVAL, "rt_reproject: NULL argument");
+    if (d->Size != sizeof(rt_reproject_desc))
+        return rt_fail(RT_EINVAL, "rt_reproject_desc: Size %u, this library's is %zu", d->Size, sizeof(rt_reproject_desc));
+    if (rt_tile_count(d->Width, d->Height, nullptr) == 0u)
+        return rt_fail(RT_EINVAL, "rt_reproject: bad image size %ux%u", d->Width, d->Height);
+    if (d->Frames == 0u) return rt_fail(RT_EINVAL, "rt_reproject: Frames is 0");
+    if (d->MaxHistory < d->Frames)
+        return rt_fail(RT_EINVAL, "rt_reproject: MaxHistory %u is below Frames %u", d->MaxHistory, d->Frames);
+    if (d->Flags & ~RT_REPROJECT_SRGB_POW) return rt_fail(RT_EINVAL, "rt_reproject: unknown flags 0x%x", d->Flags);
+    // (a NaN fails the first comparison, an infinity the second)
+    if (!(d->DepthTolerance >= 0.0f && d->DepthTolerance <= 3.402823466e+38f))
+        return rt_fail(RT_EINVAL, "rt_reproject: DepthTolerance is negative, NaN or infinite");
+    const struct {
+        const void *p;
+        uintptr_t mask;
+        const char *name;
+        bool required;
+    } planes[] = {{d->Camera, 0u, "Camera", true},
+                  {d->PreviousCamera, 0u, "PreviousCamera", true},
+                  {d->Mean, 15u, "Mean", true},
+                  {d->Hit, 7u, "Hit", true},
+                  {d->Out, 15u, "Out", true},
+                  {d->OutCount, 3u, "OutCount", true},
+                  {d->History, 15u, "History", false},
+                  {d->HistoryHit, 7u, "HistoryHit", false},
+                  {d->HistoryCount, 3u, "HistoryCount", false},
+                  {d->Rgba8, 3u, "Rgba8", false}};
+    for (const auto &pl : planes)
+        if (pl.required && !pl.p) return rt_fail(RT_EINVAL, "rt_reproject: %s is NULL", pl.name);
+    if ((d->History != nullptr) != (d->HistoryHit != nullptr) || (d->History != nullptr) != (d->HistoryCount != nullptr))
+        return rt_fail(RT_EINVAL, "rt_reproject: History, HistoryHit and HistoryCount must be all NULL or all given");
+    for (const auto &pl : planes)
+        if ((uintptr_t)pl.p & pl.mask)
+            return rt_fail(RT_EINVAL, "rt_reproject: %s is not %u-byte aligned", pl.name, (unsigned)pl.mask + 1u);
+    if ((const float *)d->Out == d->Mean)
+        return rt_fail(RT_EINVAL, "rt_reproject: Out is Mean (the pass does not run in place)");
+    if ((const float *)d->Out == d->History)
+        return rt_fail(RT_EINVAL, "rt_reproject: Out is History (the pass does not run in place)");
+    if ((const uint32_t *)d->OutCount == d->HistoryCount)
+        return rt_fail(RT_EINVAL, "rt_reproject: OutCount is HistoryCount (the pass does not run in place)");
+    ReprojectArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mean = d->Mean;
+    a.hit = d->Hit;
+    a.history = d->History;
+    a.history_hit = d->HistoryHit;
+    a.history_count = d->HistoryCount;
+    a.out = d->Out;
+    a.out_count = d->OutCount;
+    a.rgba8 = d->Rgba8;
+    a.width = d->Width;
+    a.height = d->Height;
+    a.frames = d->Frames;
+    a.max_history = d->MaxHistory;
+    a.depth_tolerance = d->DepthTolerance > 0.0f ? d->DepthTolerance : 0.0f;  // (-0.0f is off, like +0.0f)
+    a.srgb_pow = (d->Flags & RT_REPROJECT_SRGB_POW) ? 1u : 0u;
+    const rt_camera_info &c = *d->Camera, &p = *d->PreviousCamera;
+    const float cur[4][3] = {{c.CameraPosition.x, c.CameraPosition.y, c.CameraPosition.z},
+                             {c.CameraX.x, c.CameraX.y, c.CameraX.z},
+                             {c.CameraY.x, c.CameraY.y, c.CameraY.z},
+                             {c.FilmCenter.x, c.FilmCenter.y, c.FilmCenter.z}};
+    const float prev[4][3] = {{p.CameraPosition.x, p.CameraPosition.y, p.CameraPosition.z},
+                              {p.CameraX.x, p.CameraX.y, p.CameraX.z},
+                              {p.CameraY.x, p.CameraY.y, p.CameraY.z},
+                              {p.FilmCenter.x, p.FilmCenter.y, p.FilmCenter.z}};
+    for (int i = 0; i < 3; ++i) {
+        a.cam_pos[i] = cur[0][i];
+        a.cam_x[i] = cur[1][i];
+        a.cam_y[i] = cur[2][i];
+        a.film_center[i] = cur[3][i];
+        a.prev_pos[i] = prev[0][i];
+        a.prev_x[i] = prev[1][i];
+        a.prev_y[i] = prev[2][i];
+        a.fv[i] = prev[3][i] - prev[0][i];
+    }
+    a.film_w = c.FilmW;
+    a.film_h = c.FilmH;
+    a.prev_film_w = p.FilmW;
+    a.prev_film_h = p.FilmH;
+    // dot3: each product and each sum rounds on its own (this unit is built with -ffp-contract=off)
+    const float fx2 = a.fv[0] * a.fv[0], fy2 = a.fv[1] * a.fv[1], fz2 = a.fv[2] * a.fv[2];
+    a.ff = (fx2 + fy2) + fz2;
+    a.wf = (float)d->Width;
+    a.hf = (float)d->Height;
+    a.hw = a.wf * 0.5f;
+    a.hh = a.hf * 0.5f;
+    args = a;
+    return RT_OK;
+}
+
 // The key: every word the cull masks, the live list and the learned order depend on.
 static void launch_key(const LaunchPlan &p, const SceneFacts &sf, int rs, const rt_trace_desc &desc,
                        const TileSelection *sel, const TraceArgs &a, std::vector<uint32_t> &key) {

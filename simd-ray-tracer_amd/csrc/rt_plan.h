@@ -196,6 +196,13 @@ struct DenoisePlan {
 };
 int plan_denoise(const rt_denoise_desc *desc, DenoisePlan &plan);
 
+// rt_reproject without a device: everything the call refuses (the planes' pointers are compared, never followed;
+// the two cameras are HOST structs and are read) and the launch's arguments: the planes, the counts, both
+// cameras' fields and the constants the host forms once, each one f32 operation as rt_trace.h lists them --
+// fv = FilmCenter' - CameraPosition', ff = dot3(fv, fv), wf = (float)Width, hf = (float)Height, hw = wf * 0.5f,
+// hh = hf * 0.5f.  A refused call leaves `args` as it was.
+int plan_reproject(const rt_reproject_desc *desc, ReprojectArgs &args);
+
 // Which table TraceArgs.clusters names.
 enum { kTableNone = 0, kTablePlain, kTableExpanded };
 // The rule set's two cluster tables on the device: opaque to the plan, which only chooses between them.
