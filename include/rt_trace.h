@@ -698,6 +698,55 @@ int rt_reproject(const rt_reproject_desc *desc, void *stream);
  * RT_EINVAL for NULL. */
 int rt_reproject_defaults(rt_reproject_desc *out);
 
+/* ------------------------------------------------- ... with the history clamped to the fresh neighbourhood */
+
+typedef struct rt_reproject_clip_desc {
+    uint32_t Size;               /* sizeof(rt_reproject_clip_desc)                                    */
+    uint32_t Radius;             /* 1..3: the window is (2*Radius+1)^2 pixels of Mean                 */
+    float    Gamma;              /* finite, > 0: half-width of the band in standard deviations        */
+    rt_reproject_desc Reproject; /* everything rt_reproject takes, Size included                      */
+} rt_reproject_clip_desc;
+
+/* rt_reproject with variance clipping, as temporal anti-aliasing uses it.  What a mirror or a glass sphere shows
+ * does not follow its surface, so the history rt_reproject gathers there is a reflection seen from another place.
+ * This call clamps the gathered history colour, per channel, to mean +- Gamma standard deviations of the FRESH
+ * frame's pixels of the same sphere in a (2*Radius+1)^2 window around the pixel, and then folds as rt_reproject
+ * does: a stale reflection falls outside the band and is pulled in, the history of a diffuse surface lies inside
+ * it and is untouched.  It needs no knowledge of the material.  Everything rt_reproject's comment says of the call
+ * (no rt_device, no state, one launch on `stream`, HOST cameras, inputs only read, not in place) holds; the call
+ * reads no plane rt_reproject does not read.
+ *
+ * The result is rt_reproject's steps 1 to 8 on desc->Reproject with one step between "H.ch = acc.ch / ws" and the
+ * fold of step 7, for a pixel that kept at least one tap; every operation is one IEEE f32 operation, as there
+ * (tests/reproject_clip_ref.py restates it in numpy):
+ *  7a Window, R = Radius: taps dy = -R..R (outer), dx = -R..R (inner), at q = (x + dx, y + dy) of the fresh planes
+ *     Mean and Hit.  A tap is skipped when it is outside the image; when Hit[q].Key != kp (the whole word,
+ *     RT_HIT_INSIDE included); when a channel of Mean[q].xyz is not finite.  The centre takes part under the same
+ *     rules: only the finiteness rule can drop it.
+ *  7b Sums: s1 = s2 = (+0, +0, +0), nf = +0.  A tap that is kept, c = Mean[q]: s1.ch = s1.ch + c.ch,
+ *     s2.ch = s2.ch + c.ch * c.ch, nf = nf + 1.0f.
+ *  7c Band, where nf > 0: m.ch = s1.ch / nf, v.ch = pos(s2.ch / nf - m.ch * m.ch) with rt_denoise's pos
+ *     (x > 0 ? x : 0: a NaN gives 0), sd.ch = sqrtf(v.ch), lo.ch = m.ch - Gamma * sd.ch, hi.ch = m.ch + Gamma * sd.ch.
+ *  7d Clamp, by comparisons: if (H.ch < lo.ch) H.ch = lo.ch; if (H.ch > hi.ch) H.ch = hi.ch; a NaN bound clamps
+ *     nothing.  nf == 0: no clamp.  (Squares that overflow, channels beyond 1.8e19: where m.ch * m.ch is still
+ *     finite, sd = inf and the band is (-inf, +inf); where it overflows too, v = pos(inf - inf) = 0 and the band is
+ *     the point m.  With finite taps and a finite Gamma no bound is a NaN.)
+ *  A pixel alone in its window (no neighbour of its sphere) has sd = 0, so its history becomes its fresh value:
+ *  this is intended, one sample says nothing about what is plausible beside it.
+ * OutCount, Out.w, the fresh cases, Rgba8 and RT_REPROJECT_SRGB_POW are exactly rt_reproject's; OutCount does not
+ * depend on the clamp.  With Reproject.History == NULL the call writes what rt_reproject writes.
+ *
+ * RT_EINVAL, with an rt_last_error text and before anything is enqueued: a NULL desc or a wrong Size; Radius
+ * outside 1..3; a Gamma that is NaN, infinite or not > 0; and everything rt_reproject refuses for Reproject, its
+ * Size included, with rt_reproject's texts. */
+int rt_reproject_clip(const rt_reproject_clip_desc *desc, void *stream);
+/* Fills *out with Size, Reproject as rt_reproject_defaults fills it, and the library's defaults Radius = 1 and
+ * Gamma = 0.5f: the lowest three-scene mean of moves 13..24 of a 24-move orbit after the default rt_denoise, over
+ * Radius 1..3 x Gamma 0.5, 1, 2 on the CPU restatement, since the filtered frame is what a loop shows (DESIGN.md
+ * has the tables, and where a scene is worse than under rt_reproject).  A caller that shows the carried frame
+ * unfiltered does better with Radius = 2.  RT_EINVAL for NULL. */
+int rt_reproject_clip_defaults(rt_reproject_clip_desc *out);
+
 /* What the last rt_trace on `dev` launched.  Host-side bookkeeping, except
  * that TilesTraced and SegmentsFolded need the cull pass's totals: when the
  * last launch's key is new and they have not reached the host yet, this call

@@ -158,6 +158,10 @@ class RtReprojectDesc(ctypes.Structure):  # rt_reproject_desc: one rt_reproject 
 REPROJECT_SRGB_POW = 2
 
 
+class RtReprojectClipDesc(ctypes.Structure):  # rt_reproject_clip_desc: one rt_reproject_clip call, 128 B
+    _fields_ = [("Size", c_uint32), ("Radius", c_uint32), ("Gamma", c_float), ("Reproject", RtReprojectDesc)]
+
+
 OPTION_FIELDS = ("Cull", "Prefilter", "PrefilterRelative", "Clusters", "ClusterCount", "SubClusterSpheres",
                  "SecondaryThreshold", "LanesPerPixel", "PixelsPerLane", "OneWaveGroups", "SphereSourceLds",
                  "SceneInHbm", "TablesInLds", "WalkAny", "Interleave", "MergeRounds", "TileOrder", "WaveOrder",
@@ -253,6 +257,8 @@ SIGNATURES = {
     "rt_denoise_defaults": (c_int, [POINTER(RtDenoiseDesc)]),
     "rt_reproject": (c_int, [POINTER(RtReprojectDesc), c_void_p]),
     "rt_reproject_defaults": (c_int, [POINTER(RtReprojectDesc)]),
+    "rt_reproject_clip": (c_int, [POINTER(RtReprojectClipDesc), c_void_p]),
+    "rt_reproject_clip_defaults": (c_int, [POINTER(RtReprojectClipDesc)]),
     "rt_assemble_bands": (c_int, [c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                   c_void_p]),
     "rt_trace_last_info": (c_int, [c_void_p, POINTER(RtTraceInfo)]),
@@ -1021,27 +1027,72 @@ def reproject(width: int, height: int, camera: RtCameraInfo, previous_camera: Rt
     frame.  max_history, depth_tolerance: None takes the library's default (reproject_defaults()); a
     depth_tolerance of 0 turns the depth test off.  Enqueued on `stream`; needs no Device.  ValueError for a count
     or a tolerance no call can take, RtError for what the library refuses."""
+    d = _reproject_desc("reproject", width, height, camera, previous_camera, mean_ptr, hit_ptr, out_ptr, out_count_ptr,
+                        history_ptr, history_hit_ptr, history_count_ptr, rgba8_ptr, frames, max_history,
+                        depth_tolerance, srgb_pow)
+    _check(lib().rt_reproject(ctypes.byref(d), c_void_p(stream or 0)), "rt_reproject")
+
+
+def _reproject_desc(who, width, height, camera, previous_camera, mean_ptr, hit_ptr, out_ptr, out_count_ptr, history_ptr,
+                    history_hit_ptr, history_count_ptr, rgba8_ptr, frames, max_history, depth_tolerance, srgb_pow):
+    """The rt_reproject_desc of reproject() and reproject_clip(), with the wrapper's own checks (`who` names the
+    caller in their texts).  The desc points at `camera` and `previous_camera`: they must outlive it."""
     dflt = reproject_defaults()
     cap = dflt["max_history"] if max_history is None else max_history
     tol = dflt["depth_tolerance"] if depth_tolerance is None else depth_tolerance
     for name, v in (("frames", frames), ("max_history", cap)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 0xFFFFFFFF:
-            raise ValueError(f"reproject: {name} must be an integer in 1..2^32-1, got {v!r}")
+            raise ValueError(f"{who}: {name} must be an integer in 1..2^32-1, got {v!r}")
     if int(cap) < int(frames):
-        raise ValueError(f"reproject: max_history {cap!r} is below frames {frames!r}")
+        raise ValueError(f"{who}: max_history {cap!r} is below frames {frames!r}")
     if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not 0.0 <= float(tol) < float("inf"):
-        raise ValueError(f"reproject: depth_tolerance must be a finite number >= 0, got {tol!r}")
+        raise ValueError(f"{who}: depth_tolerance must be a finite number >= 0, got {tol!r}")
     if float(tol) > float(np.finfo(np.float32).max):
-        raise ValueError(f"reproject: depth_tolerance {tol!r} is not a finite f32")
+        raise ValueError(f"{who}: depth_tolerance {tol!r} is not a finite f32")
     for name, c in (("camera", camera), ("previous_camera", previous_camera)):
         if not isinstance(c, RtCameraInfo):
-            raise ValueError(f"reproject: {name} must be an RtCameraInfo (camera_setup), got {type(c).__name__}")
+            raise ValueError(f"{who}: {name} must be an RtCameraInfo (camera_setup), got {type(c).__name__}")
     d = RtReprojectDesc(ctypes.sizeof(RtReprojectDesc), width, height, int(frames), int(cap),
                         REPROJECT_SRGB_POW if srgb_pow else 0, float(tol), ctypes.pointer(camera),
                         ctypes.pointer(previous_camera), mean_ptr or None, hit_ptr or None, history_ptr or None,
                         history_hit_ptr or None, history_count_ptr or None, out_ptr or None, out_count_ptr or None,
                         rgba8_ptr or None)
-    _check(lib().rt_reproject(ctypes.byref(d), c_void_p(stream or 0)), "rt_reproject")
+    return d
+
+
+def reproject_clip_defaults() -> dict:
+    """rt_reproject_clip_defaults: the library's Radius and Gamma, and rt_reproject_defaults' values."""
+    d = RtReprojectClipDesc()
+    _check(lib().rt_reproject_clip_defaults(ctypes.byref(d)), "rt_reproject_clip_defaults")
+    assert d.Size == ctypes.sizeof(RtReprojectClipDesc) and d.Reproject.Size == ctypes.sizeof(RtReprojectDesc)
+    return dict(radius=d.Radius, gamma=d.Gamma, frames=d.Reproject.Frames, max_history=d.Reproject.MaxHistory,
+                depth_tolerance=d.Reproject.DepthTolerance)
+
+
+def reproject_clip(width: int, height: int, camera: RtCameraInfo, previous_camera: RtCameraInfo, mean_ptr: int,
+                   hit_ptr: int, out_ptr: int, out_count_ptr: int, history_ptr: int = 0, history_hit_ptr: int = 0,
+                   history_count_ptr: int = 0, rgba8_ptr: int = 0, frames: int = 1, max_history: Optional[int] = None,
+                   depth_tolerance: Optional[float] = None, srgb_pow: bool = False, radius: Optional[int] = None,
+                   gamma: Optional[float] = None, stream: Optional[int] = None) -> None:
+    """rt_reproject_clip: reproject() with the gathered history clamped, per channel, to mean +- `gamma` standard
+    deviations of the fresh frame's pixels of the same sphere in a (2 * radius + 1)^2 window, before the fold: what
+    a mirror or glass showed from the previous camera is pulled towards what it shows now.  Every other argument is
+    reproject()'s.  radius (1..3), gamma (finite, > 0): None takes the library's default
+    (reproject_clip_defaults())."""
+    dflt = reproject_clip_defaults()
+    r = dflt["radius"] if radius is None else radius
+    g = dflt["gamma"] if gamma is None else gamma
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= 3:
+        raise ValueError(f"reproject_clip: radius must be an integer in 1..3, got {r!r}")
+    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not 0.0 < float(g) < float("inf"):
+        raise ValueError(f"reproject_clip: gamma must be a finite number > 0, got {g!r}")
+    if float(g) > float(np.finfo(np.float32).max) or float(np.float32(min(float(g), 1.0))) == 0.0:
+        raise ValueError(f"reproject_clip: gamma {g!r} is not a finite f32 above 0")
+    inner = _reproject_desc("reproject_clip", width, height, camera, previous_camera, mean_ptr, hit_ptr, out_ptr,
+                            out_count_ptr, history_ptr, history_hit_ptr, history_count_ptr, rgba8_ptr, frames,
+                            max_history, depth_tolerance, srgb_pow)
+    d = RtReprojectClipDesc(ctypes.sizeof(RtReprojectClipDesc), int(r), float(g), inner)
+    _check(lib().rt_reproject_clip(ctypes.byref(d), c_void_p(stream or 0)), "rt_reproject_clip")
 
 
 # ------------------------------------------------- OnInit / OnRender mirror

@@ -1172,6 +1172,25 @@ extern "C" int rt_reproject_defaults(rt_reproject_desc *out) {
     return RT_OK;
 }
 
+// rt_reproject with the history clamped to the fresh neighbourhood's band (rt_reproject.hip): plan_reproject_clip's
+// refusals and arguments, one launch.  No device handle, no state, no allocation, no wait.
+extern "C" int rt_reproject_clip(const rt_reproject_clip_desc *desc, void *stream) {
+    ReprojectClipArgs c;
+    if (const int rc = plan_reproject_clip(desc, c)) return rc;
+    if (rtk_launch_reproject_clip(&c, (hipStream_t)stream) != 0)
+        return fail(RT_EIO, "rt_reproject_clip: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+extern "C" int rt_reproject_clip_defaults(rt_reproject_clip_desc *out) {
+    if (!out) return fail(RT_EINVAL, "rt_reproject_clip_defaults: NULL argument");
+    memset(out, 0, sizeof(*out));
+    out->Size = (uint32_t)sizeof(*out);
+    out->Radius = 1u;
+    out->Gamma = 0.5f;
+    return rt_reproject_defaults(&out->Reproject);
+}
+
 extern "C" int rt_trace_last_info(rt_device *d, rt_trace_info *out) {
     DeviceGuard device_guard;  // the caller's current device is restored on return
     if (!d || !out) return fail(RT_EINVAL, "rt_trace_last_info: NULL argument");

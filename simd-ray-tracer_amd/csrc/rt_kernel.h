@@ -381,6 +381,14 @@ struct ReprojectArgs {
     float wf, hf, hw, hh;         // (f32)Width, (f32)Height and their halves
 };
 extern "C" int rtk_launch_reproject(const ReprojectArgs *a, hipStream_t stream);
+// rt_reproject_clip (rt_reproject.hip): rt_reproject's launch with the clamp of the gathered history to the fresh
+// neighbourhood's band before the fold.  One launch; a block stages its tile of mean and hit in LDS.
+struct ReprojectClipArgs {
+    ReprojectArgs rp;             // everything rt_reproject's launch takes
+    uint32_t radius;              // 1..3: the window is (2 * radius + 1)^2 pixels of mean and hit
+    float gamma;                  // the band's half-width in standard deviations
+};
+extern "C" int rtk_launch_reproject_clip(const ReprojectClipArgs *c, hipStream_t stream);
 // Pixels of dead block tiles (live[t] == kTileDead; never kTileSkipped ones): every sample misses with no sky,
 // so fold zeros into the running mean, store both images; adds
 // dead_pixels[0] x a->frames segments to the ray counter once (dead_pixels:

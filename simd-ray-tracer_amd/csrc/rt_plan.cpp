@@ -388,6 +388,24 @@ int plan_reproject(const rt_reproject_desc *d, ReprojectArgs &args) {
     return RT_OK;
 }
 
+int plan_reproject_clip(const rt_reproject_clip_desc *d, ReprojectClipArgs &args) {
+    if (!d) return rt_fail(RT_EINVAL, "rt_reproject_clip: NULL argument");
+    if (d->Size != sizeof(rt_reproject_clip_desc))
+        return rt_fail(RT_EINVAL, "rt_reproject_clip_desc: Size %u, this library's is %zu", d->Size,
+                       sizeof(rt_reproject_clip_desc));
+    if (d->Radius < 1u || d->Radius > 3u) return rt_fail(RT_EINVAL, "rt_reproject_clip: Radius %u is not in 1..3", d->Radius);
+    // (a NaN fails the first comparison, an infinity the second)
+    if (!(d->Gamma > 0.0f && d->Gamma <= 3.402823466e+38f))
+        return rt_fail(RT_EINVAL, "rt_reproject_clip: Gamma is not a finite number above 0");
+    ReprojectClipArgs c;
+    memset(&c, 0, sizeof(c));
+    if (const int rc = plan_reproject(&d->Reproject, c.rp)) return rc;
+    c.radius = d->Radius;
+    c.gamma = d->Gamma;
+    args = c;
+    return RT_OK;
+}
+
 // The key: every word the cull masks, the live list and the learned order depend on.
 static void launch_key(const LaunchPlan &p, const SceneFacts &sf, int rs, const rt_trace_desc &desc,
                        const TileSelection *sel, const TraceArgs &a, std::vector<uint32_t> &key) {

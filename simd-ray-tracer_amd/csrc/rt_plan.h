@@ -202,6 +202,10 @@ int plan_denoise(const rt_denoise_desc *desc, DenoisePlan &plan);
 // fv = FilmCenter' - CameraPosition', ff = dot3(fv, fv), wf = (float)Width, hf = (float)Height, hw = wf * 0.5f,
 // hh = hf * 0.5f.  A refused call leaves `args` as it was.
 int plan_reproject(const rt_reproject_desc *desc, ReprojectArgs &args);
+// rt_reproject_clip without a device, on plan_reproject: the outer desc's own refusals (NULL, Size, Radius outside
+// 1..3, a Gamma that is not finite or not > 0), then everything plan_reproject refuses for desc->Reproject, with its
+// texts; args.rp is plan_reproject's result, radius and gamma the desc's.  A refused call leaves `args` as it was.
+int plan_reproject_clip(const rt_reproject_clip_desc *desc, ReprojectClipArgs &args);
 
 // Which table TraceArgs.clusters names.
 enum { kTableNone = 0, kTablePlain, kTableExpanded };

@@ -7,6 +7,16 @@
 // in LDS.  Every operation is one f32 operation in the stated order (-ffp-contract=off, the compiler's IEEE
 // division and square root; the direction is rtk_math.h's normalize, start_sample's own), so the kernel and the
 // numpy restatement (tests/reproject_ref.py) give the same bits.
+//
+// rt_reproject_clip is the same pass with one step more: before the fold the gathered history colour is clamped,
+// per channel, to mean +- Gamma * sigma of the fresh frame's pixels of the same sphere in a (2R + 1)^2 window
+// (variance clipping; rt_trace.h states it operation by operation, tests/reproject_clip_ref.py restates it).  Both
+// calls run reproject_pixel, so steps 1 to 8 are one piece of code; the clamp is a functor the fold calls, empty in
+// reproject_kernel.  reproject_clip_kernel takes 32 x 8 pixels per block and loads the (32 + 2R) x (8 + 2R) tile of
+// Mean.xyz and Hit.Key once into LDS, 16 B per entry (8.3 KB at R = 3); every tap of the window reads LDS.  Every
+// thread reaches the barrier, whatever its own pixel is; an entry outside the image holds a NaN colour and
+// RT_HIT_MISS, and is not read either (the tap loop tests the image's bounds).  A shape with one thread per pixel and
+// every tap a global load was built beside it and lost at every radius (profiles/reproject_clip_ab.txt).
 #include "rtk_math.h"
 
 namespace rtk {
@@ -15,12 +25,17 @@ constexpr uint32_t kReprojectMiss = 0xFFFFFFFFu;  // RT_HIT_MISS
 
 __device__ __forceinline__ bool rp_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e+38f; }  // (a NaN fails)
 
-__global__ __launch_bounds__(256) void reproject_kernel(ReprojectArgs a) {
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= a.width || y >= a.height) return;
-    const size_t p = (size_t)y * a.width + x;
-    const float4 m = ((const float4 *)a.mean)[p];
-    const uint2 hp = ((const uint2 *)a.hit)[p];
+// The clamp of rt_reproject: none.
+struct NoClip {
+    __device__ __forceinline__ void operator()(uint32_t, float &, float &, float &) const {}
+};
+
+// Steps 1 to 8 for the pixel (x, y) inside the image, p its index, m = Mean[p] and hp = Hit[p] (the caller loads
+// them: reproject_clip_kernel does so before its barrier).  `clip(kp, hx, hy, hz)` runs on the gathered history
+// colour of a pixel that kept at least one tap, between H = acc / ws and the fold.
+template <class Clip>
+__device__ __forceinline__ void reproject_pixel(const ReprojectArgs &a, uint32_t x, uint32_t y, size_t p, const float4 &m,
+                                                const uint2 &hp, const Clip &clip) {
     const uint32_t kp = hp.x;
     float ox = m.x, oy = m.y, oz = m.z;  // fresh: the mean itself
     uint32_t count = a.frames;
@@ -79,7 +94,8 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojectArgs a) {
             }
             if (kept) {
                 n = n < a.max_history ? n : a.max_history;
-                const float hx = accx / ws, hy = accy / ws, hz = accz / ws;
+                float hx = accx / ws, hy = accy / ws, hz = accz / ws;
+                clip(kp, hx, hy, hz);
                 const float fr = (float)a.frames;
                 const float al = fr / ((float)n + fr);
                 ox = hx + (m.x - hx) * al;
@@ -95,11 +111,121 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojectArgs a) {
     if (a.rgba8) a.rgba8[p] = rgba8(ox, oy, oz, a.srgb_pow != 0u);
 }
 
+__global__ __launch_bounds__(256) void reproject_kernel(ReprojectArgs a) {
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * a.width + x;
+    reproject_pixel(a, x, y, p, ((const float4 *)a.mean)[p], ((const uint2 *)a.hit)[p], NoClip{});
+}
+
+// ------------------------------------------------- rt_reproject_clip
+constexpr int kClipTX = 32, kClipTY = 8;  // pixels per block
+
+__device__ __forceinline__ float rp_pos(float v) { return v > 0.0f ? v : 0.0f; }  // rt_denoise's pos (a NaN gives 0)
+
+// The new step for the pixel (x, y) at (lu, lv) of the block's LDS tile of (Mean.xyz, Hit.Key): the sums over the
+// window in the stated order, the band, the clamp by comparisons (a NaN bound clamps nothing).
+template <int R>
+struct ClipHistory {
+    const float4 *tile;
+    float gamma;
+    int x, y, lu, lv, w_img, h_img;
+    __device__ __forceinline__ void operator()(uint32_t kp, float &hx, float &hy, float &hz) const {
+        float s1x = 0.0f, s1y = 0.0f, s1z = 0.0f, s2x = 0.0f, s2y = 0.0f, s2z = 0.0f, nf = 0.0f;
+#pragma unroll
+        for (int dy = -R; dy <= R; ++dy) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= h_img) continue;
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= w_img) continue;
+                const float4 c = tile[(lv + R + dy) * (kClipTX + 2 * R) + lu + R + dx];
+                if (__float_as_uint(c.w) != kp) continue;
+                if (!(rp_finite(c.x) && rp_finite(c.y) && rp_finite(c.z))) continue;
+                s1x = s1x + c.x;
+                s1y = s1y + c.y;
+                s1z = s1z + c.z;
+                s2x = s2x + c.x * c.x;
+                s2y = s2y + c.y * c.y;
+                s2z = s2z + c.z * c.z;
+                nf = nf + 1.0f;
+            }
+        }
+        if (nf > 0.0f) {
+            clamp(s1x, s2x, nf, hx);
+            clamp(s1y, s2y, nf, hy);
+            clamp(s1z, s2z, nf, hz);
+        }
+    }
+    __device__ __forceinline__ void clamp(float s1, float s2, float nf, float &hc) const {
+        const float m = s1 / nf;
+        const float sd = __builtin_sqrtf(rp_pos(s2 / nf - m * m));
+        const float lo = m - gamma * sd, hi = m + gamma * sd;
+        if (hc < lo) hc = lo;
+        if (hc > hi) hc = hi;
+    }
+};
+
+template <int R>
+__global__ __launch_bounds__(256) void reproject_clip_kernel(ReprojectClipArgs c) {
+    constexpr int LW = kClipTX + 2 * R, LH = kClipTY + 2 * R, LN = LW * LH;
+    __shared__ float4 s_tile[LN];
+    const int w_img = (int)c.rp.width, h_img = (int)c.rp.height;
+    const int x0 = (int)blockIdx.x * kClipTX, y0 = (int)blockIdx.y * kClipTY;
+    const int lu = (int)(threadIdx.x & 31u), lv = (int)(threadIdx.x >> 5);
+    const int x = x0 + lu, y = y0 + lv;
+    const bool inside = x < w_img && y < h_img;
+    // the thread's own pixel first, so that its loads are under way while the tile is filled
+    const size_t p = inside ? (size_t)y * c.rp.width + (size_t)x : 0u;
+    float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint2 hp = make_uint2(kReprojectMiss, 0u);
+    if (inside) {
+        m = ((const float4 *)c.rp.mean)[p];
+        hp = ((const uint2 *)c.rp.hit)[p];
+    }
+    // Every thread of the block comes here and to the barrier: misses, fresh pixels and threads outside the image
+    // too.  (Without a history no pixel reaches the clamp and the tile is not filled: the condition is the block's.)
+    if (c.rp.history != nullptr) {
+        for (int e = (int)threadIdx.x; e < LN; e += 256) {
+            const int qx = x0 - R + e % LW, qy = y0 - R + e / LW;
+            // outside the image: a key no pixel that reaches the clamp has, and a colour the finiteness rule drops
+            float4 v = make_float4(__uint_as_float(0x7FC00000u), 0.0f, 0.0f, __uint_as_float(kReprojectMiss));
+            if (qx >= 0 && qx < w_img && qy >= 0 && qy < h_img) {
+                const size_t q = (size_t)qy * c.rp.width + (size_t)qx;
+                v = ((const float4 *)c.rp.mean)[q];
+                v.w = __uint_as_float(((const uint32_t *)c.rp.hit)[2u * q]);
+            }
+            s_tile[e] = v;
+        }
+    }
+    __syncthreads();
+    if (!inside) return;
+    reproject_pixel(c.rp, (uint32_t)x, (uint32_t)y, p, m, hp, ClipHistory<R>{s_tile, c.gamma, x, y, lu, lv, w_img, h_img});
+}
+
+template <int R>
+static void launch_clip(const ReprojectClipArgs &c, hipStream_t stream) {
+    const dim3 grid((c.rp.width + kClipTX - 1u) / kClipTX, (c.rp.height + kClipTY - 1u) / kClipTY);
+    hipLaunchKernelGGL(reproject_clip_kernel<R>, grid, dim3(256), 0, stream, c);
+}
+
 }  // namespace rtk
 
 extern "C" int rtk_launch_reproject(const ReprojectArgs *a, hipStream_t stream) {
     if (a->width == 0u || a->height == 0u) return -1;
     const dim3 grid((a->width + 63u) / 64u, (a->height + 3u) / 4u);
     hipLaunchKernelGGL(rtk::reproject_kernel, grid, dim3(256), 0, stream, *a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int rtk_launch_reproject_clip(const ReprojectClipArgs *c, hipStream_t stream) {
+    if (c->rp.width == 0u || c->rp.height == 0u) return -1;
+    switch (c->radius) {
+        case 1: rtk::launch_clip<1>(*c, stream); break;
+        case 2: rtk::launch_clip<2>(*c, stream); break;
+        case 3: rtk::launch_clip<3>(*c, stream); break;
+        default: return -1;
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
