@@ -14,10 +14,9 @@ import pytest
 F = np.float32
 
 
-def fma(a, b, c):
-    # exact f32 product in f64, one rounding of the sum to f64, one to f32:
-    # within 1 ulp of a true fma -- far inside the bound's slack
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
+# the correctly rounded f32 fma (tests/walk_ref.py; tests/test_walk_ref.py holds it to rational arithmetic): the
+# kernel's own v_fma_f32, so the restatements below are the kernel's arithmetic, not arithmetic within an ulp of it
+from walk_ref import fma  # noqa: E402,F401  (test_expanded_prefilter, test_own_sphere_skip, test_direction_table import it from here)
 
 
 def exact_dist(cx, cy, cz, dx, dy, dz):
@@ -170,10 +169,9 @@ def check_prefilter(rt, scene, simd, seed, n_rays=4000, require_hits=True):
         assert hit.sum() > 0
     if relative and require_hits:  # the per-lane threshold must cull too
         assert (~skipped & live[None, :]).sum() < 1.5 * hit.sum() + 0.2 * live.sum() * len(o)
-    return bool(flags & 5), int((skipped & live[None, :]).sum())
-
     if flags & 1 and require_hits:  # where it is enabled, the prefilter must actually cull
         assert (~skipped).sum() < 1.5 * hit.sum() + 0.05 * hit.size
+    return bool(flags & 5), int((skipped & live[None, :]).sum())
 
 
 def test_prefilter_rows_of_padding_are_never_flagged(rt):
